@@ -31,10 +31,18 @@ calls (the JNI staging shape; PCIe-inclusive), instead of HBM-resident batches.
 Launch: `python bench.py --gpus N` spawns N ranks itself (torch.distributed.run,
 before any GPU call); under torchrun (WORLD_SIZE set) it is one rank.  Rank 0
 prints ONE JSON line: `value` = samples/s over all ranks (max-over-ranks time);
-`roofline` = the dominant kernel's algorithmic bytes / its
-average duration (HIP events on the engine's stream); `path_roofline` = B_alg
-(8 B/sample + 7280 B/series) / ms_per_step -- the headline fraction;
-`cpu_baseline` = the C oracle (restatement of the JVM path) on host cores.
+`ms_per_step` = the time of one of the --steps timed steps; `path_roofline` =
+B_alg (8 B/sample + 7280 B/series) / ms_per_step -- the headline fraction.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds
+what takes work of its own: the check that every sample of the last step landed
+in exactly one bucket, `kernels` and `roofline` = the dominant kernel's
+algorithmic bytes / its average duration (HIP events on the
+engine's stream, in steps after the timed ones) with the committed PMC traffic,
+and `cpu_baseline` = the C oracle (restatement of the JVM path) on host cores.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs);
+the inputs are seeded, so two builds run with the same arguments compare array
+for array.
 """
 from __future__ import annotations
 
@@ -106,7 +114,18 @@ def parse():
     p.add_argument("--dry-run", action="store_true", help="ranks + shard plan only (gloo, no GPU, no engine)")
     p.add_argument("--loopback", type=int, default=0,
                    help="c4: the whole W-rank fleet merge on this GPU (W contexts, loopback transport)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also: the every-sample-landed check of the last step, per-kernel "
+                        "device times and `roofline` (steps of their own), the PMC traffic and the CPU baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (summaries, dense counts; seeded row samples of "
+                        "the large arrays) as DIR/<name>.npy in float64")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 # ---------------------------------------------------------------- launch
@@ -306,6 +325,54 @@ def load_pmc_traffic(path, pl):
     return out, f"PMC {os.path.basename(path)} (src {pm['src_hash']})"
 
 
+# ---------------------------------------------------------------- outputs
+DUMP_HEAD_ROWS = 256          # the hottest series (Zipf head: the split / direct-tile paths) are always kept
+DUMP_SUMMARY_ROWS = 131_072   # 11 float64 per row
+DUMP_COUNT_ROWS = 2_048       # 1798 float64 per row
+# largest dump (C3, 1M series): 8.0 + 11.5 + 1.0 + 29.5 MB + the row lists < 64 MB
+
+
+def dump_rows(rows: int, limit: int, seed: int):
+    """The rows of a `rows`-row output that a dump keeps: all of them up to `limit`, else
+    the first DUMP_HEAD_ROWS and a seeded draw of the rest (the same rows in every run)."""
+    import numpy as np
+    if rows <= limit:
+        return np.arange(rows, dtype=np.int64)
+    rest = np.random.default_rng(seed).choice(rows - DUMP_HEAD_ROWS, size=limit - DUMP_HEAD_ROWS, replace=False)
+    return np.concatenate([np.arange(DUMP_HEAD_ROWS, dtype=np.int64), np.sort(rest) + DUMP_HEAD_ROWS])
+
+
+def dump_outputs(out_dir, summ, counts, rows, tag="", parts=1):
+    """Write what the timed path returned in its last step -- the first `rows` rows of the
+    summary records `summ` (int64 [*, 11], avg as float64 bits) and of the dense bucket
+    counts `counts` (int32 [*, 1798]; None for a merge that returns summaries only) -- as
+    <out_dir>/<name><tag>.npy, all float64.  Small outputs are written whole; of large ones
+    every series' sample count (`series_counts`), every bucket's total over all series
+    (`bucket_totals`), and the `*_rows` listed rows of `summary` and `counts`.  `parts`:
+    dumps that share the directory (their row limits are divided by it)."""
+    import numpy as np
+    import torch
+    from linkerd_amd import _native as N_
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    rows = int(rows)
+    save("series_counts", summ[:rows, 0].cpu().numpy())
+    pick = dump_rows(rows, max(DUMP_HEAD_ROWS + 1, DUMP_SUMMARY_ROWS // parts), seed=1)
+    rec = summ[:rows][torch.from_numpy(pick).to(summ.device)].cpu().numpy()
+    rec = np.ascontiguousarray(rec).view(N_.SUMMARY_DTYPE).reshape(-1)
+    save("summary_rows", pick)
+    save("summary", np.stack([rec[f].astype(np.float64) for f in N_.SUMMARY_FIELDS], axis=1)
+         if rec.size else np.zeros((0, len(N_.SUMMARY_FIELDS))))
+    if counts is not None:
+        save("bucket_totals", counts[:rows].sum(dim=0, dtype=torch.int64).cpu().numpy())
+        pick = dump_rows(rows, max(DUMP_HEAD_ROWS + 1, DUMP_COUNT_ROWS // parts), seed=2)
+        save("counts_rows", pick)
+        save("counts", counts[:rows][torch.from_numpy(pick).to(counts.device)].cpu().numpy())
+
+
 # ---------------------------------------------------------------- main
 def result_stream():
     """The result line's stream: a duplicate of stdout, while fd 1 itself is pointed at
@@ -366,21 +433,26 @@ def run_c4_loopback(args, result_out, check=True):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if check:  # (tools/phases_c4.py times development builds whose results are not checked)
+    if args.dump_outputs:  # every rank's slice, as the last timed step left it
+        for r in range(W):
+            dump_outputs(args.dump_outputs, summ[r], cnts[r], counts[r], tag=f"_rank{r}", parts=W)
+    if check and args.full:  # (tools/phases_c4.py times development builds whose results are not checked)
         got = sum(int(summ[r][:counts[r], 0].sum()) for r in range(W))
         assert got == Ntot, f"summary counts sum {got} != {Ntot}"
         assert sum(int(cnts[r][:counts[r]].sum(dtype=torch.int64)) for r in range(W)) == Ntot
-    for e in engines:
-        e.set_param(N_.PARAM_TIMING, 1)
-        e.kernel_times(reset=True)
-    tsteps = 3
-    for _ in range(tsteps):
-        step()
-    per_rank = []
-    for e in engines:
-        kt = e.kernel_times(reset=True)
-        per_rank.append({k: round(ms / tsteps, 4) for k, (ms, n) in kt.items() if n})
-        e.set_param(N_.PARAM_TIMING, 0)
+    per_rank = None
+    if args.full:  # per-kernel device times: steps of their own
+        for e in engines:
+            e.set_param(N_.PARAM_TIMING, 1)
+            e.kernel_times(reset=True)
+        tsteps = 3
+        for _ in range(tsteps):
+            step()
+        per_rank = []
+        for e in engines:
+            kt = e.kernel_times(reset=True)
+            per_rank.append({k: round(ms / tsteps, 4) for k, (ms, n) in kt.items() if n})
+            e.set_param(N_.PARAM_TIMING, 0)
     mb = [e.merge_bytes() for e in engines]
     ms = elapsed / args.steps * 1e3
     # what the device copies stand in for: each rank's slices to the W-1 others over its
@@ -416,7 +488,7 @@ def run_c4_loopback(args, result_out, check=True):
                   "dense_bytes_per_rank": mb[0]["dense"] * (W - 1) // W,
                   "note": "sent = what a rank sends the other W-1 ranks (sparse); dense = the dense rows + totals "
                           "a dense reduce-scatter would send"},
-        "roofline": None, "cpu_baseline": None,
+        "roofline": None, "cpu_baseline": None, "full": args.full,
     }
     print(json.dumps(line), file=result_out, flush=True)
     for e in engines:
@@ -575,30 +647,41 @@ def run(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # what the last timed step returned, before any later step overwrites it
+    if args.dump_outputs:
+        tag = f"_rank{rank}" if distributed else ""
+        if fleet:
+            dump_outputs(args.dump_outputs, summ, None, state["merged"][1], tag=tag)
+        else:
+            dump_outputs(args.dump_outputs, summ, counts, S, tag=tag)
+
     # sanity: every sample of the last step landed in exactly one bucket
-    if fleet:
-        first, cnt = state["merged"]
-        tot = torch.stack([summ[:cnt, 0].sum(), torch.tensor(0, device=dev)])
-        want = pl["N_total"]
-    else:
-        tot = torch.stack([counts[:S].sum(dtype=torch.int64), summ[:S, 0].sum()])
-        want = n
-    if distributed and fleet:
-        tot = tot.to(coll_dev)
-        dist.all_reduce(tot)
-    assert int(tot[0].item()) == want, f"summary counts sum {int(tot[0].item())} != {want}"
-    if not fleet:
-        assert int(tot[1].item()) == want
+    if args.full:
+        if fleet:
+            first, cnt = state["merged"]
+            tot = torch.stack([summ[:cnt, 0].sum(), torch.tensor(0, device=dev)])
+            want = pl["N_total"]
+        else:
+            tot = torch.stack([counts[:S].sum(dtype=torch.int64), summ[:S, 0].sum()])
+            want = n
+        if distributed and fleet:
+            tot = tot.to(coll_dev)
+            dist.all_reduce(tot)
+        assert int(tot[0].item()) == want, f"summary counts sum {int(tot[0].item())} != {want}"
+        if not fleet:
+            assert int(tot[1].item()) == want
 
     # per-kernel device time (HIP events on the engine's stream), separate steps
-    eng.set_param(N_.PARAM_TIMING, 1)
-    eng.kernel_times(reset=True)
-    tsteps = max(3, min(args.steps, 5))
-    for _ in range(tsteps):
-        step()
-    kt = eng.kernel_times(reset=True)
-    eng.set_param(N_.PARAM_TIMING, 0)
-    barrier()
+    kt, tsteps = {}, 0
+    if args.full:
+        eng.set_param(N_.PARAM_TIMING, 1)
+        eng.kernel_times(reset=True)
+        tsteps = max(3, min(args.steps, 5))
+        for _ in range(tsteps):
+            step()
+        kt = eng.kernel_times(reset=True)
+        eng.set_param(N_.PARAM_TIMING, 0)
+        barrier()
 
     ms_per_step = elapsed / args.steps * 1e3
     total_samples = pl["N_total"] if pl["scaling"] == "strong" and not args.shard else n * world
@@ -614,7 +697,7 @@ def run(args):
             entry["alg_GBs"] = round(ab / (avg * 1e-3) / 1e9, 1)
             entry["alg_bytes"] = int(ab)
         kernels[name] = entry
-    pmc, pmc_note = load_pmc_traffic(args.pmc_json, pl)
+    pmc, pmc_note = load_pmc_traffic(args.pmc_json, pl) if args.full else ({}, None)
     for name, entry in kernels.items():
         if name in pmc:
             entry["traffic"] = pmc[name]
@@ -650,7 +733,7 @@ def run(args):
     # C1 and C2: the whole step (no extrapolation); C3: a bounded sample of the step
     default_sample = {"c1": n, "c2": n}.get(pl["workload"], 50_000_000)
     sample = args.cpu_sample if args.cpu_sample is not None else default_sample
-    if rank == 0 and world == 1 and sample > 0 and not streaming:
+    if args.full and rank == 0 and world == 1 and sample > 0 and not streaming:
         _, nproc, avail, share = host_cpu()
         if args.cpu_threads:
             tcounts = [args.cpu_threads]
@@ -689,7 +772,8 @@ def run(args):
             "path_roofline": {"bound": "hbm", "achieved": round(path_gbs, 1), "peak": HBM_PEAK_GBS * gpus,
                               "unit": "GB/s", "frac": round(path_gbs / (HBM_PEAK_GBS * gpus), 4),
                               "alg_bytes_per_step": balg, "formula": "8 B/sample + 7280 B/series (SURVEY.md §8d)"},
-            "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu,
+            # (--full only: None in a plain run)
+            "roofline": roofline, "kernels": kernels if args.full else None, "cpu_baseline": cpu, "full": args.full,
             # partition passes redone in the timed steps (a capacity-planned region overflowed)
             # (level2_counted: batches whose level-2 regions were known not to fit after
             # level 1 -- the first level-2 pass only counted, the second wrote exact regions)

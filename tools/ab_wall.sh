@@ -8,7 +8,7 @@ LIBS=$1; R=${2:-3}; shift 2
 for i in $(seq 1 $R); do
   for v in $LIBS; do
     lib=${v%%:*}; var=0; [ "$lib" != "$v" ] && var=${v#*:}
-    L5DH_LIB=$PWD/linkerd_amd/lib_ab/lib$lib.so timeout -k 10 240 python3 -u bench.py --cpu-sample 0 --variant $var "$@" > $O/ab_$v$i.json 2> $O/ab.err || { tail -20 $O/ab.err; exit 1; }
+    L5DH_LIB=$PWD/linkerd_amd/lib_ab/lib$lib.so timeout -k 10 240 python3 -u bench.py --full --cpu-sample 0 --variant $var "$@" > $O/ab_$v$i.json 2> $O/ab.err || { tail -20 $O/ab.err; exit 1; }
     python3 -c "
 import json
 d=json.loads(open('$O/ab_$v$i.json').read().strip().splitlines()[-1])

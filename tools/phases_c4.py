@@ -21,7 +21,7 @@ def main():
     argv = sys.argv[1:]
     if "--loopback" not in argv:
         argv += ["--loopback", "8"]
-    sys.argv = ["bench.py", "--workload", "c4", "--steps", "3", "--warmup", "1"] + argv
+    sys.argv = ["bench.py", "--full", "--workload", "c4", "--steps", "3", "--warmup", "1"] + argv
     args = bench.parse()
     from linkerd_amd import _native as N
     core = N.load()
