@@ -13,7 +13,7 @@
  *    (pageable or from l5dh_pin_alloc) or device memory (hipMalloc on the
  *    context's device); the library detects which.
  *  - Status codes: 0 = OK, negative errno otherwise (-EINVAL, -ENOMEM, -EIO,
- *    -ENODEV).  The HIP/RCCL error text of the last failure is kept in
+ *    -ENODEV, -ERANGE).  The HIP/RCCL error text of the last failure is kept in
  *    l5dh_last_error(ctx).  No C++ exception crosses the ABI.
  *  - Every entry point taking a context is thread-safe (one lock per context).
  *  - The library never retains a caller pointer after a call returns, except
@@ -75,6 +75,9 @@ enum {
   L5DH_PARAM_REGION_PCT = 13,  /* capacity of the partition's regions in percent of the prediction (1..1000,
                                   default 100); a region that overflows is redone with exact sizes, so values
                                   below 100 exercise that path (tests) and cost time, never results */
+  L5DH_PARAM_ROLLUP_ITEM = 14, /* members per work item of a rollup (1..64, default 64; a group of more than
+                                  1024 items' worth takes longer items); small values cut test-sized groups
+                                  into several items (tests) and cost time, never results */
   L5DH_PARAM_VARIANT = 12      /* kernel variant bits for same-context A/B timing (0: the default kernels;
                                   every variant computes the same results; bit 0: one-tile folds in u16 bins;
                                   bit 1: DMA copies of pinned host batches; bit 2: every ingest batch's
@@ -168,6 +171,39 @@ int l5dh_export_state(l5dh_ctx* ctx, uint32_t first, uint32_t count, int32_t* co
  * of exported counts): counts [n][1798] int32, totals [n] int64. */
 int l5dh_summarize_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals, size_t n,
                          l5dh_summary* out);
+
+/* Label rollups: the histogram of a union of series is the element-wise integer sum
+ * of their bucket rows, so a group's summary is exact -- what ONE Stat would report
+ * had it received every member's samples (Metric.scala:53-67 over the summed counts).
+ * group[i] names the group of series first + i: a value < ngroups, or L5DH_NO_GROUP
+ * (the series is in no group); anything else is -EINVAL, found on the device and
+ * reported by this call (nothing is reset then).  Per group g < ngroups the outputs
+ * (each nullable) receive: g_out[g] the summary, g_counts_out[g][1798] the summed
+ * bucket counts, g_totals_out[g] the summed exact sums (an int64 that wraps like a
+ * Java long).  A group without members, or whose members are all empty, gets a zero
+ * row, total 0 and the all-zero summary.  A bucket sum above 2^31 - 1 (what an int32
+ * row, and upstream's Int counts, can hold) is detected, never wrapped: the call
+ * returns -ERANGE, l5dh_last_error names the first such group, the outputs are
+ * unspecified and nothing is reset.  count == 0 (n == 0) still writes ngroups empty
+ * results.  ngroups is in [1, L5DH_MAX_SERIES]. */
+#define L5DH_NO_GROUP 0xFFFFFFFFu
+
+/* Live state.  Under ONE hold of the context lock: staged samples are binned
+ * and pending segments folded; the rows of series [first, first+count) are
+ * summed per group into g_* (each nullable; ngroups rows); then, if
+ * series_out is given and/or reset != 0, the per-series snapshot of the same
+ * range is taken from the same state (series_out: count l5dh_summary,
+ * nullable) and the range is cleared -- so the rollup, the per-series
+ * summaries and the reset all see exactly the same samples. */
+int l5dh_rollup(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* group, uint32_t ngroups,
+                l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out,
+                l5dh_summary* series_out, int reset);
+
+/* External dense rows: counts [n][1798] int32, totals [n] int64 (nullable: 0) --
+ * the inputs of l5dh_summarize_dense, e.g. the slice a rank received from l5dh_merge. */
+int l5dh_rollup_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals, size_t n,
+                      const uint32_t* group, uint32_t ngroups,
+                      l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out);
 
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:

@@ -37,6 +37,10 @@ PARAM_MAX_SLABS = 10
 PARAM_MERGE_RCCL_1RANK = 11
 PARAM_VARIANT = 12
 PARAM_REGION_PCT = 13
+PARAM_ROLLUP_ITEM = 14
+
+NO_GROUP = 0xFFFFFFFF  # L5DH_NO_GROUP
+MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
 
 MERGE_REDUCE_SCATTER = 0
 MERGE_ALL_REDUCE = 1
@@ -75,6 +79,8 @@ SIGNATURES = {
     "l5dh_peek": (_c.c_int, [_vp, _c.c_uint32, _vp, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "l5dh_export_state": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_int]),
     "l5dh_summarize_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp]),
+    "l5dh_rollup": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _vp, _vp, _c.c_int]),
+    "l5dh_rollup_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _vp]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

@@ -24,6 +24,7 @@
 #include "../../include/l5dhist.h"
 #include "l5dh_kernels.hpp"
 #include "l5dh_merge.hpp"
+#include "l5dh_rollup.hpp"
 
 using namespace l5dh;
 
@@ -265,6 +266,9 @@ struct l5dh_ctx {
   uint64_t m_dense_bytes = 0, m_encoded_bytes = 0, m_sent_bytes = 0;
   bool rccl_1rank = false;  // run the collective in a 1-rank communicator too (an identity otherwise skipped)
   bool loopback = false;    // l5dh_comm_init_loopback: the collectives are device copies among the group's contexts
+  // label rollups (l5dh_rollup.hip): the staged map, the plan's arrays, the partial rows, staged outputs
+  DevBuf ru_group, ru_u32, ru_u64, ru_members, ru_igroup, ru_mlist, ru_partial, ru_tmp, ru_summ, ru_counts, ru_totals;
+  uint32_t rollup_item = RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params
   uint32_t cold_limit = COLD_LIMIT_MAX;
@@ -736,6 +740,119 @@ int do_snapshot(l5dh_ctx* c, uint32_t first, uint32_t count, l5dh_summary* out, 
   // device outputs on a caller stream are stream ordered (as device inputs of
   // l5dh_ingest): the caller's later work on that stream sees them; no host wait
   if ((!out || out_dev) && (!counts_out || cnt_dev) && c->stream != c->own_stream) return 0;
+  return sync_stream(c);
+}
+
+// ---- label rollups -------------------------------------------------------------
+// Per-group sums of the live state rows of series [first, first + count) (ext ==
+// nullptr; then also the per-series snapshot / reset of the same state) or of external
+// dense rows ext[count][1798].  The caller holds the lock and has checked the arguments.
+int do_rollup(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const int64_t* ext_totals,
+              const uint32_t* group, uint32_t G, l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out,
+              l5dh_summary* series_out, int reset) {
+  int r;
+  const bool live = ext == nullptr;
+  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
+  // inputs: host buffers are staged
+  RollupWork w{};
+  w.count = count;
+  w.G = G;
+  w.first = first;
+  w.item = c->rollup_item;
+  w.caps = rollup_caps(count, G, w.item);
+  w.tmp_bytes = rollup_tmp_bytes(G);
+  const size_t G1 = (size_t)G + 1;
+  if ((r = ensure(c, c->ru_u32, (4 * G1 + RH_WORDS) * 4)) || (r = ensure(c, c->ru_u64, 2 * G1 * 8)) ||
+      (r = ensure(c, c->ru_members, ((size_t)count + 1) * 4)) || (r = ensure(c, c->ru_igroup, w.caps.items * 4)) ||
+      (r = ensure(c, c->ru_mlist, (w.caps.multi + 1) * 4)) ||
+      (r = ensure(c, c->ru_partial, (w.caps.slots + 1) * (size_t)RU_PROW * 8)) ||
+      (r = ensure(c, c->ru_tmp, w.tmp_bytes)))
+    return r;
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if (count && !(is_device_ptr(group) && (uintptr_t)group % 4 == 0)) {
+      if ((r = ensure(c, c->ru_group, (size_t)count * 4))) return r;
+      HIPCHK(c, hipMemcpyAsync(c->ru_group.p, group, (size_t)count * 4, hipMemcpyDefault, c->stream));
+      group = static_cast<const uint32_t*>(c->ru_group.p);
+    }
+    if (ext && count && !(is_device_ptr(ext) && (uintptr_t)ext % 8 == 0)) {
+      if ((r = ensure(c, c->stage_in_counts, (size_t)count * NB * 4))) return r;
+      HIPCHK(c, hipMemcpyAsync(c->stage_in_counts.p, ext, (size_t)count * NB * 4, hipMemcpyDefault, c->stream));
+      ext = static_cast<const int32_t*>(c->stage_in_counts.p);
+    }
+    if (ext && ext_totals && count && !(is_device_ptr(ext_totals) && (uintptr_t)ext_totals % 8 == 0)) {
+      if ((r = ensure(c, c->stage_in_totals, (size_t)count * 8))) return r;
+      HIPCHK(c, hipMemcpyAsync(c->stage_in_totals.p, ext_totals, (size_t)count * 8, hipMemcpyDefault, c->stream));
+      ext_totals = static_cast<const int64_t*>(c->stage_in_totals.p);
+    }
+  }
+  w.group = group;
+  uint32_t* u = static_cast<uint32_t*>(c->ru_u32.p);
+  w.cnt = u;
+  w.nitems = u + G1;
+  w.cursor = u + 2 * G1;
+  w.pbase = u + 3 * G1;
+  w.hdr = u + 4 * G1;
+  w.moff = static_cast<uint64_t*>(c->ru_u64.p);
+  w.ioff = w.moff + G1;
+  w.members = static_cast<uint32_t*>(c->ru_members.p);
+  w.igroup = static_cast<uint32_t*>(c->ru_igroup.p);
+  w.mlist = static_cast<uint32_t*>(c->ru_mlist.p);
+  w.partial = static_cast<uint64_t*>(c->ru_partial.p);
+  w.tmp = c->ru_tmp.p;
+  // outputs: device pointers are written directly, host pointers via staging
+  const bool go_dev = g_out && is_device_ptr(g_out) && ((uintptr_t)g_out % 8 == 0);
+  const bool gc_dev = g_counts_out && is_device_ptr(g_counts_out) && ((uintptr_t)g_counts_out % 8 == 0);
+  const bool gt_dev = g_totals_out && is_device_ptr(g_totals_out) && ((uintptr_t)g_totals_out % 8 == 0);
+  const bool so_dev = series_out && is_device_ptr(series_out) && ((uintptr_t)series_out % 8 == 0);
+  RollupOut o{nullptr, nullptr, nullptr};
+  if (g_out) {
+    if (!go_dev && (r = ensure(c, c->ru_summ, (size_t)G * 88))) return r;
+    o.summ = go_dev ? reinterpret_cast<Summary88*>(g_out) : static_cast<Summary88*>(c->ru_summ.p);
+  }
+  if (g_counts_out) {
+    if (!gc_dev && (r = ensure(c, c->ru_counts, (size_t)G * NB * 4))) return r;
+    o.counts = gc_dev ? g_counts_out : static_cast<int32_t*>(c->ru_counts.p);
+  }
+  if (g_totals_out) {
+    if (!gt_dev && (r = ensure(c, c->ru_totals, (size_t)G * 8))) return r;
+    o.totals = gt_dev ? g_totals_out : static_cast<int64_t*>(c->ru_totals.p);
+  }
+  Summary88* d_series = nullptr;
+  if (series_out && count) {
+    if (!so_dev && (r = ensure(c, c->stage_summ, (size_t)count * 88))) return r;
+    d_series = so_dev ? reinterpret_cast<Summary88*>(series_out) : static_cast<Summary88*>(c->stage_summ.p);
+  }
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, launch_rollup(w, state(c), ext, ext_totals, tables(c), o, c->stream));
+  }
+  // the device's findings (an invalid map entry, a bucket sum out of range) end the call
+  // here, before the snapshot that would reset the range
+  uint32_t hdr[RH_WORDS];
+  HIPCHK(c, hipMemcpyAsync(hdr, w.hdr, sizeof(hdr), hipMemcpyDeviceToHost, c->stream));
+  if ((r = sync_stream(c))) return r;
+  if (hdr[RH_BOUNDS]) return fail(c, -EIO, "internal: a rollup workspace bound was hit");
+  if (hdr[RH_BADIDX] != 0xFFFFFFFFu)
+    return fail(c, -EINVAL,
+                "rollup: group[" + std::to_string(hdr[RH_BADIDX]) + "] is neither < ngroups nor L5DH_NO_GROUP");
+  if (hdr[RH_RANGE] != 0xFFFFFFFFu)
+    return fail(c, -ERANGE, "rollup: a bucket sum of group " + std::to_string(hdr[RH_RANGE]) + " exceeds 2^31 - 1");
+  if (live && count && (d_series || reset)) {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{d_series, nullptr, first, count, nullptr},
+                          reset, nullptr, c->stream));
+  }
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if (g_out && !go_dev) HIPCHK(c, hipMemcpyAsync(g_out, o.summ, (size_t)G * 88, hipMemcpyDefault, c->stream));
+    if (g_counts_out && !gc_dev)
+      HIPCHK(c, hipMemcpyAsync(g_counts_out, o.counts, (size_t)G * NB * 4, hipMemcpyDefault, c->stream));
+    if (g_totals_out && !gt_dev)
+      HIPCHK(c, hipMemcpyAsync(g_totals_out, o.totals, (size_t)G * 8, hipMemcpyDefault, c->stream));
+    if (d_series && !so_dev)
+      HIPCHK(c, hipMemcpyAsync(series_out, d_series, (size_t)count * 88, hipMemcpyDefault, c->stream));
+  }
   return sync_stream(c);
 }
 
@@ -1233,7 +1350,10 @@ int l5dh_close(l5dh_ctx* c) {
                     &c->ring_series,     &c->ring_values,  &c->merge_counts,   &c->merge_totals,
                     &c->recv_counts,     &c->recv_totals,  &c->m_words,        &c->m_offs,
                     &c->m_enc,           &c->m_tmp,        &c->m_sizes,        &c->r_words,
-                    &c->r_offs,          &c->r_enc,        &c->m_unpacked,     &c->m_roff};
+                    &c->r_offs,          &c->r_enc,        &c->m_unpacked,     &c->m_roff,
+                    &c->ru_group,        &c->ru_u32,       &c->ru_u64,         &c->ru_members,
+                    &c->ru_igroup,       &c->ru_mlist,     &c->ru_partial,     &c->ru_tmp,
+                    &c->ru_summ,         &c->ru_counts,    &c->ru_totals};
   for (DevBuf* b : bufs)
     if (b->p) hipFree(b->p);
   if (c->h_header) hipHostFree(c->h_header);
@@ -1361,6 +1481,34 @@ int l5dh_summarize_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* tota
   return sync_stream(c);
 }
 
+int l5dh_rollup(l5dh_ctx* c, uint32_t first, uint32_t count, const uint32_t* group, uint32_t ngroups,
+                l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out, l5dh_summary* series_out,
+                int reset) {
+  if (!c) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipSetDevice(c->device);
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (ngroups == 0 || ngroups > L5DH_MAX_SERIES) return fail(c, -EINVAL, "rollup: ngroups must be in [1, 2^20]");
+  if (!group) return fail(c, -EINVAL, "rollup: null group map");
+  return do_rollup(c, first, count, nullptr, nullptr, group, ngroups, g_out, g_counts_out, g_totals_out, series_out,
+                   reset);
+}
+
+int l5dh_rollup_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, size_t n, const uint32_t* group,
+                      uint32_t ngroups, l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out) {
+  if (!c) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  hipSetDevice(c->device);
+  if (n > 0xFFFFFFF0ull) return fail(c, -EINVAL, "rollup: more than 2^32 - 16 dense rows");
+  if (ngroups == 0 || ngroups > L5DH_MAX_SERIES) return fail(c, -EINVAL, "rollup: ngroups must be in [1, 2^20]");
+  if (!group) return fail(c, -EINVAL, "rollup: null group map");
+  if (n && !counts) return fail(c, -EINVAL, "rollup: null dense rows");
+  // (n == 0: the kernels never read a row; a non-null marker selects the dense source)
+  static const int32_t none = 0;
+  return do_rollup(c, 0, (uint32_t)n, n ? counts : &none, n ? totals : nullptr, group, ngroups, g_out, g_counts_out,
+                   g_totals_out, nullptr, 0);
+}
+
 int l5dh_peek(l5dh_ctx* c, uint32_t series, l5dh_bucket_count* out, size_t cap, size_t* n_out) {
   if (!c) return -EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
@@ -1477,6 +1625,10 @@ int l5dh_set_param(l5dh_ctx* c, int param, int64_t v) {
     case L5DH_PARAM_REGION_PCT:
       if (v < 1 || v > 1000) return fail(c, -EINVAL, "region capacity percent must be in [1, 1000]");
       c->region_pct = (uint32_t)v;
+      return 0;
+    case L5DH_PARAM_ROLLUP_ITEM:
+      if (v < 1 || v > (int64_t)RU_ITEM_DEFAULT) return fail(c, -EINVAL, "rollup item must be in [1, 64] members");
+      c->rollup_item = (uint32_t)v;
       return 0;
     case L5DH_PARAM_MERGE_RCCL_1RANK:
       c->rccl_1rank = v != 0;

@@ -220,6 +220,92 @@ class HistogramEngine:
         self._check(self._lib.l5dh_summarize_dense(self._ctx, cp, tp, n, op), "l5dh_summarize_dense")
         return out if own else None
 
+    # -- label rollups ------------------------------------------------------------
+    def _group_map(self, group, ngroups: int, count: int):
+        """The uint32 group map of ``count`` series (every entry < ngroups or NO_GROUP;
+        entries >= ngroups are found on the device).  A numpy int32 / int64 map is
+        converted, -1 standing for NO_GROUP."""
+        ngroups = int(ngroups)
+        if ngroups < 1 or ngroups > N.MAX_SERIES:
+            raise ValueError(f"ngroups must be in [1, {N.MAX_SERIES}], got {ngroups}")
+        if isinstance(group, np.ndarray):
+            if group.dtype in (np.dtype(np.int32), np.dtype(np.int64)):
+                if group.size and (group.min() < -1 or group.max() > N.NO_GROUP):
+                    raise ValueError("group: entries must be -1 (no group) or fit uint32")
+                group = np.where(group == -1, N.NO_GROUP, group).astype(np.uint32)
+            elif group.dtype != np.dtype(np.uint32):
+                raise ValueError(f"group: dtype {group.dtype} is not uint32 (or int32 / int64 with -1 for no group)")
+            group = np.ascontiguousarray(group)
+        elif _is_torch(group):
+            if _NP_OF_TORCH.get(str(group.dtype)) is not np.uint32:
+                raise ValueError(f"group: dtype {group.dtype} is not uint32")
+        else:
+            raise ValueError(f"group: unsupported map type {type(group)!r}")
+        if _numel(group) != count:
+            raise ValueError(f"group: {_numel(group)} entries for {count} series")
+        return group, ngroups
+
+    def rollup_into(self, group, ngroups: int, summaries=None, counts=None, totals=None, series=None,
+                    first: int = 0, count: Optional[int] = None, reset: bool = False, dense=None) -> None:
+        """Exact per-group rollup into caller buffers (numpy, or torch tensors on the
+        engine's GPU): summaries int64 [ngroups*11] (or the numpy summary dtype), counts
+        int32 [ngroups][1798], totals int64 [ngroups].  dense=None sums the live rows of
+        series [first, first+count) (l5dh_rollup; ``series`` then receives the per-series
+        summaries of the same state and ``reset`` clears the range, atomically with the
+        rollup); dense=(counts, totals) sums external dense rows (l5dh_rollup_dense)."""
+        if dense is not None:
+            dcounts, dtotals = dense
+            n = _numel(dcounts) // N.NBUCKETS
+            if n * N.NBUCKETS != _numel(dcounts):
+                raise ValueError("dense counts must hold whole rows of 1798 buckets")
+            if series is not None or reset:
+                raise ValueError("a dense rollup has no series snapshot and nothing to reset")
+            first, count = 0, n
+        else:
+            first, count = self._range(first, count)
+        group, ngroups = self._group_map(group, ngroups, count)
+        gp = self._buf(group, (np.uint32,), "group", count)
+        sp = self._summ_buf(summaries, ngroups, "summaries")
+        cp = self._buf(counts, (np.int32,), "counts", ngroups * N.NBUCKETS, writable=True)
+        tp = self._buf(totals, (np.int64,), "totals", ngroups, writable=True)
+        if dense is not None:
+            dcp = self._buf(dcounts, (np.int32,), "dense counts")
+            dtp = self._buf(dtotals, (np.int64,), "dense totals", count)
+            self._check(self._lib.l5dh_rollup_dense(self._ctx, dcp, dtp, count, gp, ngroups, sp, cp, tp),
+                        "l5dh_rollup_dense")
+            return
+        rp = self._summ_buf(series, count, "series")
+        self._check(self._lib.l5dh_rollup(self._ctx, first, count, gp, ngroups, sp, cp, tp, rp, int(reset)),
+                    "l5dh_rollup")
+
+    def _rollup_numpy(self, group, ngroups, with_counts, with_series, **kw):
+        first, count = (0, 0) if "dense" in kw else self._range(kw.get("first", 0), kw.get("count"))
+        ngroups = int(ngroups)
+        if ngroups < 1 or ngroups > N.MAX_SERIES:
+            raise ValueError(f"ngroups must be in [1, {N.MAX_SERIES}], got {ngroups}")
+        out = np.zeros(ngroups, dtype=N.SUMMARY_DTYPE)
+        counts = np.zeros((ngroups, N.NBUCKETS), dtype=np.int32) if with_counts else None
+        totals = np.zeros(ngroups, dtype=np.int64) if with_counts else None
+        series = np.zeros(count, dtype=N.SUMMARY_DTYPE) if with_series else None
+        self.rollup_into(group, ngroups, out, counts, totals, series, **kw)
+        res = (out,) + ((counts, totals) if with_counts else ()) + ((series,) if with_series else ())
+        return res if len(res) > 1 else out
+
+    def rollup(self, group, ngroups: int, first: int = 0, count: Optional[int] = None, reset: bool = False,
+               with_counts: bool = False, with_series: bool = False):
+        """Exact summaries of the unions of series [first, first+count) named by
+        ``group`` (entry i: the group of series first+i, or NO_GROUP / -1): what one Stat
+        fed every member's samples would report.  Returns the group summaries, followed
+        by (counts [ngroups][1798], totals [ngroups]) with ``with_counts`` and by the
+        per-series summaries of the same state with ``with_series``; ``reset`` clears
+        the range atomically with both."""
+        return self._rollup_numpy(group, ngroups, with_counts, with_series, first=first, count=count, reset=reset)
+
+    def rollup_dense(self, counts, totals, group, ngroups: int, with_counts: bool = False):
+        """The same over external dense rows (counts [n][1798] int32, totals [n] int64 or
+        None), e.g. the slice a rank received from ``merge``."""
+        return self._rollup_numpy(group, ngroups, with_counts, False, dense=(counts, totals))
+
     # -- fleet merge (RCCL) ------------------------------------------------------
     @staticmethod
     def comm_unique_id() -> bytes:

@@ -91,12 +91,19 @@ class PrometheusTelemeter:
 
     path = "/admin/metrics/prometheus"
 
-    def __init__(self, metrics: MetricsTree):
+    def __init__(self, metrics: MetricsTree, rollups=None):
         self.metrics = metrics
+        # optional (RollupPlan, group summaries) pair of linkerd_amd.rollup, settable
+        # later: its lines follow the tree's
+        self.rollups = rollups
 
     def render(self) -> str:
         out: List[str] = []
         write_metrics(self.metrics, out)
+        if self.rollups is not None:
+            from .rollup import write_rollup_metrics
+            plan, summaries = self.rollups
+            write_rollup_metrics(plan, summaries, out)
         return "".join(out)
 
 

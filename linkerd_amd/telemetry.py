@@ -162,6 +162,16 @@ class StatEngine:
         self.flush()
         return self.engine.snapshot(first=0, count=self.capacity, reset=reset)
 
+    def snapshot_all_rollup(self, group_of, ngroups: int, reset: bool = True):
+        """(series summaries, group summaries) of every series from ONE engine call:
+        the exact rollups of the groups named by ``group_of`` (uint32 [capacity], entry
+        = group or NO_GROUP; linkerd_amd.rollup.plan_rollup) and the per-series
+        snapshot (+ reset) see exactly the same samples."""
+        self.flush()
+        groups, series = self.engine.rollup(group_of, ngroups, first=0, count=self.capacity, reset=reset,
+                                            with_series=True)
+        return series, groups
+
 
 class _Staging:
     def __init__(self, n: int):
