@@ -42,6 +42,7 @@ constexpr uint32_t RSAMPLE = 1u << 18;
 #define L5DH_RS_WG 64
 #endif
 constexpr int RS_WG = L5DH_RS_WG;  // k_rsample workgroups (<= 65535 draws each: u16 LDS counters)
+static_assert((RSAMPLE + RS_WG - 1) / RS_WG <= 65535, "k_rsample's u16 LDS counters: at most 65535 draws per workgroup");
 constexpr uint32_t INVALID = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }

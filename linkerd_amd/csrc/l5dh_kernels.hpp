@@ -7,17 +7,14 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "l5dh_tables.hpp"  // NL, NB, INT_MAXV, LIM_PAD, ROW, LUT_N, LUT2_N, V_ESC
+
 namespace l5dh {
 
-constexpr int NL = 1797;            // BucketedHistogram.scala:42
-constexpr int NB = 1798;            // counts = limits + overflow bucket
-constexpr int INT_MAXV = 2147483647;
-constexpr int LIM_PAD = 2048;       // limits padded with Int.MaxValue for an 11-step search
 constexpr int TILE = 32;            // series per tile (unit of LDS privatization)
 constexpr int TILE_SHIFT = 5;
 constexpr int ST_TILES = 64;        // tiles per super-tile (the level-1 partition unit)
 constexpr int ST_SHIFT = 11;        // 64 tiles x 32 series
-constexpr int ROW = 1800;           // state row stride in u32 (16-B aligned rows)
 constexpr int CROW = 900;           // u16-packed cold row in LDS, in u32 words
 constexpr int HROW = 1800;          // u32 hot row in LDS
 // Level-1 record of a super-tile bin (u32, rec32):
@@ -27,7 +24,6 @@ constexpr int HROW = 1800;          // u32 hot row in LDS
 // Final record (u16, rec16): [15:11] series in tile | [10:0] bucket.  Level 1 writes
 //   them for the direct tiles (bucketized there, value sums folded in LDS into
 //   sumfix), level 2 for the other tiles (value sums folded per super-tile).
-constexpr uint32_t V_ESC = (1u << 21) - 2048u;
 constexpr int MAX_SEG = 8;
 constexpr int WG = 1024;            // threads per workgroup of the heavy kernels
 constexpr uint32_t COLD_LIMIT_MAX = 65535u;  // u16 LDS bins cannot overflow below this
@@ -42,9 +38,6 @@ constexpr size_t ACC_SPLIT_LDS = (size_t)16 * HROW * 4;
 // u64 value sums, the bucket LUT
 constexpr size_t FOLD16_LDS = (size_t)16 * HROW * 4 + 16 * 64 * 8 + 1024 * 8;
 constexpr size_t FOLD32_LDS = (size_t)TILE * CROW * 4 + TILE * 64 * 8 + 1024 * 8;
-
-constexpr int LUT_N = 1664;         // bucket bracket LUT: 64 direct + 25 octaves x 64
-constexpr int LUT2_N = 1024;        // exact bucket + offset LUT for keys < 2^21 (64 direct + 15 octaves x 64)
 
 struct Tables {            // constant tables in HBM (a few KB each, L2 resident)
   const int32_t* lim_pad;  // [2048] limits padded with Int.MaxValue
@@ -227,12 +220,5 @@ hipError_t launch_rows(State state, const int32_t* ext, const int64_t* ext_total
 hipError_t launch_fetch_host(const uint32_t* hs, const uint32_t* hv, uint32_t* ds, uint32_t* dv, size_t n,
                              hipStream_t st);
 hipError_t set_snapshot_attributes();
-
-// LUT for bucket_lut: builds lut[LUT_N] from the limits; returns the largest
-// number of limits inside one LUT interval (the device search assumes <= 2).
-int build_bucket_lut(const int32_t* limits, uint32_t* lut);
-// LUT for bucket_lut2 (keys < 2^21), verified exhaustively; 0 on success.
-int build_bucket_lut2(const int32_t* limits, uint32_t* lut2);
-int build_bucket_lut3(const int32_t* limits, uint32_t* lut3);
 
 }  // namespace l5dh

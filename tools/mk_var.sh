@@ -8,10 +8,9 @@ N=$1; shift
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -w -DL5DH_DEV $*"
 T=$(mktemp -d)
 mkdir -p ../lib_ab
-/opt/rocm/bin/hipcc $F -c l5dh_ingest.hip -o $T/i.o &
-/opt/rocm/bin/hipcc $F -c l5dh_snapshot.hip -o $T/s.o &
-/opt/rocm/bin/hipcc $F -x hip -c l5dh_engine.cpp -o $T/e.o &
-/opt/rocm/bin/hipcc $F -c l5dh_merge.hip -o $T/m.o &
+for f in l5dh_ingest.hip l5dh_snapshot.hip l5dh_merge.hip l5dh_rollup.hip l5dh_engine.cpp l5dh_fleet.cpp l5dh_tables.cpp; do
+  /opt/rocm/bin/hipcc $F -x hip -c $f -o $T/${f%.*}.o &
+done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib_ab/lib$N.so $T/i.o $T/s.o $T/m.o $T/e.o -L/opt/rocm/lib -lrccl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib_ab/lib$N.so $T/*.o -L/opt/rocm/lib -lrccl
 rm -rf $T
