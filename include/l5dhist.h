@@ -168,7 +168,10 @@ int l5dh_export_state(l5dh_ctx* ctx, uint32_t first, uint32_t count, int32_t* co
                       int64_t* totals, int reset);
 
 /* Summaries of externally held dense state (e.g. after an RCCL reduce-scatter
- * of exported counts): counts [n][1798] int32, totals [n] int64. */
+ * of exported counts): counts [n][1798] int32, totals [n] int64.  Domain: every
+ * count in [0, 2^31 - 1] (upstream's Int counts; negative counts are outside the
+ * contract and not checked) and any row sum -- a row's count may pass 2^32 (up to
+ * 1798 (2^31 - 1)); it and the percentile targets are carried in 64 bits. */
 int l5dh_summarize_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals, size_t n,
                          l5dh_summary* out);
 
@@ -240,7 +243,10 @@ int l5dh_comm_destroy(l5dh_ctx* ctx);
  * all-reduce moves them dense.  out (nullable) receives *count l5dh_summary,
  * counts_out / totals_out (nullable) the summed rows.  Each output must hold
  * ceil(S/nranks) rows (reduce-scatter) or S rows (all-reduce).  Integer sums:
- * bit-exact and independent of the reduction order.  The export consumes the
+ * bit-exact and independent of the reduction order.  Unlike a rollup, the merge adds
+ * the ranks' bucket counts in 32 bits and checks no range: a merged bucket above
+ * 2^32 - 1 wraps silently (above 2^31 - 1 it no longer fits the int32 counts_out).
+ * The merged row's count is exact for the buckets as merged.  The export consumes the
  * rank's interval (as a resetting snapshot does) before the collective runs: if
  * the collective then fails (-EIO, l5dh_last_error), that interval is lost -- the
  * same outcome as a snapshot whose outputs are discarded. */

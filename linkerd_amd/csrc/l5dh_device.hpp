@@ -115,6 +115,44 @@ struct SrcExt {  // external dense rows, stride 1798 int32 (8-B aligned)
 };
 
 __device__ __forceinline__ uint32_t sum4(uint4 v) { return v.x + v.y + v.z + v.w; }
+// The lane's nine group sums at a width that cannot wrap.  Four legal buckets (each
+// <= 2^31 - 1 in an int32 row, a u32 in a state row) sum to 2^32 and more, but stay below
+// 2^34: the low words, and bits 32..33 of all nine packed in one register (nine u64 sums
+// took k_accum_cold_h from 125 to 137 VGPRs, past the 128 at which two of its workgroups
+// share a CU; this form compiles to 122).
+// Plain uint32_t[9] sums are for sources whose record count bounds the row: a cold
+// half-tile (<= 65535 records), one chunk of a big one (<= 2^20).
+struct WideSums {
+  uint32_t lo[9];
+  uint32_t hi;  // bits 2q, 2q + 1: bits 32, 33 of group q's sum
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) lo[q] = 0u;
+    hi = 0u;
+  }
+  __device__ __forceinline__ void set(int q, uint4 v) {  // after clear(), once per q
+    const uint64_t s = (uint64_t)v.x + v.y + v.z + v.w;
+    lo[q] = (uint32_t)s;
+    hi |= (uint32_t)(s >> 32) << (2 * q);
+  }
+};
+__device__ __forceinline__ void sums_clear(uint32_t (&g)[9]) {
+#pragma unroll
+  for (int q = 0; q < 9; ++q) g[q] = 0u;
+}
+__device__ __forceinline__ void sums_clear(WideSums& g) { g.clear(); }
+__device__ __forceinline__ void sums_set(uint32_t (&g)[9], int q, uint4 v) { g[q] = sum4(v); }
+__device__ __forceinline__ void sums_set(WideSums& g, int q, uint4 v) { g.set(q, v); }
+// group q's sum of this lane / of lane `from`
+__device__ __forceinline__ uint32_t sums_get(const uint32_t (&g)[9], int q) { return g[q]; }
+__device__ __forceinline__ uint64_t sums_get(const WideSums& g, int q) {
+  return ((uint64_t)((g.hi >> (2 * q)) & 3u) << 32) | g.lo[q];
+}
+__device__ __forceinline__ uint32_t sums_get(const uint32_t (&g)[9], int q, int from) { return __shfl(g[q], from, 64); }
+__device__ __forceinline__ uint64_t sums_get(const WideSums& g, int q, int from) {
+  const uint32_t h = __shfl(g.hi, from, 64);
+  return ((uint64_t)((h >> (2 * q)) & 3u) << 32) | __shfl(g.lo[q], from, 64);
+}
 
 __device__ __forceinline__ uint64_t dot4(uint4 v, const int32_t* __restrict__ base, int b0) {
   const uint4 bb = *reinterpret_cast<const uint4*>(base + b0);  // base table padded to 1800 with 0
@@ -131,7 +169,9 @@ __device__ __forceinline__ void store4_state(uint32_t* __restrict__ row, int b0,
 }
 
 // Wave-cooperative summary of one series (Metric.Stat.summary, Metric.scala:53-67;
-// upstream percentile/minimum/maximum/average).  g[q] = sum of the lane's group q.
+// upstream percentile/minimum/maximum/average).  g = the sums of the lane's groups: WideSums
+// wherever four buckets of a row may sum to 2^32 or more (state rows, external rows, rollup
+// and merge sums), uint32_t[9] only where the record count bounds the row.
 //   min  = first bucket whose running count >= 1
 //   pXX  = first bucket whose running count >= Math.round(p * num)
 //   max  = first bucket whose running count >= num (= last non-empty bucket)
@@ -140,22 +180,24 @@ __device__ __forceinline__ void store4_state(uint32_t* __restrict__ row, int b0,
 // prefix; lanes 0..7 then locate the group (shuffles) and the bin (one get4).
 // SMALL: the row's count is below 2^32 (a cold half-tile: <= 65535 records), so the lane
 // prefix, the targets and the owner search are 32-bit (one scan, one readlane, one permute).
-template <class Src, bool SMALL = false>
-__device__ __forceinline__ void wave_summary(const uint32_t (&g)[9], const Src& src, int64_t total,
+template <class Src, bool SMALL = false, class G>
+__device__ __forceinline__ void wave_summary(const G& g, const Src& src, int64_t total,
                                              const int32_t* __restrict__ mid, Summary88* __restrict__ out) {
   using U = typename std::conditional<SMALL, uint32_t, uint64_t>::type;
+  static_assert(!(SMALL && std::is_same<G, WideSums>::value), "group sums wider than the lane prefix");
   auto rl = [](U x, int k) -> U {  // lane k's value
     if constexpr (SMALL) {
       return (U)__builtin_amdgcn_readlane((uint32_t)x, k);
     } else {
-      return ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), k) << 32) |
-             __builtin_amdgcn_readlane((uint32_t)x, k);
+      // (readlane returns int: unconverted, a low word >= 2^31 would sign-extend over the high one)
+      return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(x >> 32), k) << 32) |
+             (uint32_t)__builtin_amdgcn_readlane((uint32_t)x, k);
     }
   };
   const int lane = lane_id();
   U ls = 0;
 #pragma unroll
-  for (int q = 0; q < 9; ++q) ls += g[q];
+  for (int q = 0; q < 9; ++q) ls += sums_get(g, q);
   U incl;
   if constexpr (SMALL)
     incl = wave_incl_scan32(ls);
@@ -188,7 +230,7 @@ __device__ __forceinline__ void wave_summary(const uint32_t (&g)[9], const Src& 
   bool done = false;
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
-    const uint32_t gq = __shfl(g[q], my_owner, 64);
+    const U gq = sums_get(g, q, my_owner);
     if (!done) {
       if (acc + gq >= my_t) {
         qsel = q;
@@ -300,8 +342,8 @@ __device__ __forceinline__ void put_words(uint32_t w, uint32_t* __restrict__ out
 // Pass over a row source: optional dense copy in a coalesced lane order (lane l
 // copies groups l, l+64, ...), then the blocked group sums of the summary; with
 // words_out, the row's merge-encoding words (counted from the values already read).
-template <class Src>
-__device__ __forceinline__ void row_pass(const Src& src, uint32_t (&g)[9], int32_t* __restrict__ out_row,
+template <class Src, class G>
+__device__ __forceinline__ void row_pass(const Src& src, G& g, int32_t* __restrict__ out_row,
                                          uint32_t* __restrict__ words_out = nullptr) {
   const int lane = lane_id();
   uint32_t w = 0;
@@ -317,12 +359,12 @@ __device__ __forceinline__ void row_pass(const Src& src, uint32_t (&g)[9], int32
     }
   }
   const int ng = lane_groups(lane);
+  sums_clear(g);
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
-    g[q] = 0u;
     if (q < ng) {
       const uint4 v = src.get4(28 * lane + 4 * q);
-      g[q] = sum4(v);
+      sums_set(g, q, v);
       if (!out_row) w += merge_words4(v);
     }
   }

@@ -194,10 +194,12 @@ __global__ __launch_bounds__(64 * MDEC_WAVES) void k_mdecode(MergeRecv src, uint
       int32_t* orow = out_rows + (size_t)r * NB;
       for (int q = lane; q < NB4; q += 64) store4_1798(orow, 4 * q, lds.get4(4 * q));
     }
-    uint32_t g[9];
+    WideSums g;  // (the merged u32 buckets of a group can sum to 2^32 and more)
+    g.clear();
     const int ng = lane_groups(lane);
 #pragma unroll
-    for (int q = 0; q < 9; ++q) g[q] = q < ng ? sum4(lds.get4(28 * lane + 4 * q)) : 0u;
+    for (int q = 0; q < 9; ++q)
+      if (q < ng) g.set(q, lds.get4(28 * lane + 4 * q));
     wave_summary(g, lds, totals ? totals[r] : 0, tb.mid, out_summ ? out_summ + r : nullptr);
     // cleared for the next row (this wave's LDS operations stay in order: the reads come first)
     for (int b = lane; b < ROW / 4; b += 64) reinterpret_cast<uint4*>(row)[b] = make_uint4(0u, 0u, 0u, 0u);

@@ -169,13 +169,13 @@ __device__ __forceinline__ void finish_group(const Acc& x, uint64_t total, uint3
 #pragma unroll
     for (int j = 0; j < 4; ++j) mx = x.a[q][j] > mx ? x.a[q][j] : mx;
   if (__ballot(mx > (uint64_t)INT_MAXV) != 0ull && lane == 0) atomicMin(hdr + RH_RANGE, g);
-  uint32_t gs[9];
+  WideSums gs;  // (four bucket sums of 2^31 - 1 each pass 2^32)
+  gs.clear();
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
     const uint4 v = make_uint4((uint32_t)x.a[q][0], (uint32_t)x.a[q][1], (uint32_t)x.a[q][2], (uint32_t)x.a[q][3]);
-    gs[q] = 0u;
     if (q < ng) {
-      gs[q] = sum4(v);
+      gs.set(q, v);
       store4_state(lrow, 28 * lane + 4 * q, v);  // (bins 1798, 1799: zero sums)
     }
   }

@@ -247,8 +247,16 @@ __device__ __forceinline__ void emit_series(const SrcL& lds, uint32_t s, uint64_
   const bool emit = final_mode && s >= out.first && oi < out.count;
   int32_t* orow = (emit && out.counts) ? out.counts + (size_t)oi * NB : nullptr;
   uint32_t* srow = st.counts + (size_t)s * ROW;
-  uint32_t g[9], nw = 0;
+  int64_t total = (int64_t)vsum + fix;  // fix = sumfix[s], read (and cleared) by the caller
+  if (dirty) total += st.total[s];
+  if (lane == 0 && keep) st.total[s] = total;
+  if (lane == 0 && emit && out.totals) out.totals[oi] = total;
+  Summary88* so = (emit && out.summ) ? out.summ + oi : nullptr;
+  uint32_t nw = 0;
   if (!dirty) {
+    // 32-bit group sums: the row holds the new records alone (a cold half-tile: <= 65535
+    // for SrcLds16; a source with larger rows would need the wide sums of the dirty branch)
+    uint32_t g[9];
     // coalesced pass: lane l handles groups q = l + 64k (bins 4q..4q+3; 1798/1799 are
     // padding); even output rows are 16-B aligned and take one 16-B store per group
     const bool al16 = (oi & 1u) == 0u;
@@ -277,35 +285,33 @@ __device__ __forceinline__ void emit_series(const SrcL& lds, uint32_t s, uint64_
         nw += merge_words4(v);
       }
     }
+    if (emit) {
+      put_words(nw, out.words ? out.words + oi : nullptr);
+      wave_summary(g, lds, total, tb.mid, so);
+    }
   } else {
+    // wide group sums: the merged state row's u32 buckets can sum past 2^32 in a group
     const SrcRow32 old{srow};
+    WideSums g;
+    g.clear();
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-      g[q] = 0;
       if (q < ng) {
         const int b0 = 28 * lane + 4 * q;
         const uint4 v = lds.get4(b0);
         const uint4 o = old.get4(b0);
         const uint4 cmb = make_uint4(v.x + o.x, v.y + o.y, v.z + o.z, v.w + o.w);
-        g[q] = sum4(cmb);
+        g.set(q, cmb);
         nw += merge_words4(cmb);
         if (orow) store4_1798(orow, b0, cmb);
         store4_state(srow, b0, cmb);  // the merged row is also the summary source
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  }
-  int64_t total = (int64_t)vsum + fix;  // fix = sumfix[s], read (and cleared) by the caller
-  if (dirty) total += st.total[s];
-  if (lane == 0 && keep) st.total[s] = total;
-  if (lane == 0 && emit && out.totals) out.totals[oi] = total;
-  if (emit) {
-    Summary88* so = out.summ ? out.summ + oi : nullptr;
-    put_words(nw, out.words ? out.words + oi : nullptr);
-    if (dirty)
+    if (emit) {
+      put_words(nw, out.words ? out.words + oi : nullptr);
       wave_summary(g, SrcRow32{srow}, total, tb.mid, so);
-    else
-      wave_summary(g, lds, total, tb.mid, so);
+    }
   }
 }
 
@@ -623,6 +629,7 @@ __global__ __launch_bounds__(512, 2) void k_accum_cold_h(Segs segs, Plan plan, S
       if (s < st.S) {
         if (linear) {
           const int ng = lane_groups(lane);
+          // 32-bit group sums and the SMALL summary: the row is the item's records, <= 65535
           uint32_t g[9], nw = 0;
           if (out.words) {  // (the merge encoding's words: the all-reduce export only)
 #pragma unroll
@@ -880,7 +887,7 @@ __global__ __launch_bounds__(WG) void k_accum_split(Segs segs, Plan plan, State 
       if (s < st.S) {
         const SrcLds32 src{hist + w * HROW};
         const int64_t total = st.sumfix[s];
-        uint32_t g[9];
+        uint32_t g[9];  // 32-bit group sums: the row is one chunk's records (hot_chunk <= 2^20)
         row_pass(src, g, out.counts + (size_t)s * NB, out.words ? out.words + s : nullptr);
         wave_summary(g, src, total, tb.mid, out.summ ? out.summ + s : nullptr);
         if (lane == 0) {
@@ -948,7 +955,7 @@ __global__ __launch_bounds__(WG) void k_hot_finish(Plan plan, State st, Tables t
       if (final_mode) {
         const uint32_t oi = s - out.first;
         if (s >= out.first && oi < out.count) {
-          uint32_t g[9];
+          WideSums g;  // (u32 buckets accumulated over chunks and intervals: a group can pass 2^32)
           uint32_t* wo = out.words ? out.words + oi : nullptr;
           if (direct_out && !(plan.tile_flags[t] & TF_DIRTY)) {  // counted in the output row itself
             const SrcExt src{out.counts + (size_t)oi * NB};
@@ -979,7 +986,7 @@ __global__ __launch_bounds__(256) void k_rows(State st, const int32_t* __restric
   const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= out.count) return;
   const int lane = lane_id();
-  uint32_t g[9];
+  WideSums g;  // (four buckets of an external or a state row can sum to 2^32 and more)
   int32_t* orow = out.counts ? out.counts + (size_t)i * NB : nullptr;
   if (ext) {
     const SrcExt src{ext + (size_t)i * NB};
@@ -1012,8 +1019,7 @@ __global__ __launch_bounds__(256) void k_rows(State st, const int32_t* __restric
       }
     }
   } else {
-#pragma unroll
-    for (int q = 0; q < 9; ++q) g[q] = 0;
+    g.clear();
     if (orow) {
       const int ng = lane_groups(lane);
 #pragma unroll
