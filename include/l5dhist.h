@@ -208,6 +208,51 @@ int l5dh_rollup_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* total
                       const uint32_t* group, uint32_t ngroups,
                       l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out);
 
+/* Exact cumulative `le` buckets (Prometheus `<name>_bucket{le="..."}` counters): unlike
+ * quantiles, they can be summed and divided outside the process (sum by (le),
+ * histogram_quantile, "share of requests under 250 ms").  Bucket b of a row holds the
+ * samples with L[b-1] <= (long)value < L[b] (L = l5dh_limits; bucket 0: (long)value < 1;
+ * bucket 1797: the overflow).  A cut c in [1, 1797] stands for the first c buckets: the
+ * count at the cut is counts[0] + ... + counts[c-1], carried in 64 bits, which is
+ * exactly the number of samples with (long)value <= L[c-1] - 1 -- so the cut's label is
+ * le = L[c-1] - 1, exact for the truncated value the histogram records.
+ *
+ * l5dh_le_cuts (host only, no context): each bound B is snapped DOWN to the largest such
+ * le <= floor(B), so no reported bucket ever claims more than it holds:
+ * cuts[i] = #{ j : L[j] - 1 <= floor(B) } clipped to [1, 1797], le[i] = L[cuts[i]-1] - 1
+ * (cuts / le: each nullable).  Bounds 1, 2, 5, 10, 25, 50, 100 are exact (cuts 2, 3, 6,
+ * 11, 26, 51, 101); 250 -> cut 193, le 250; 500 -> cut 262, le 497; 1000 -> cut 332,
+ * le 997; +Inf and anything >= L[1796] - 1 give cut 1797.  NaN or B < 0 is -EINVAL
+ * (nothing is written).  Nothing is deduplicated: bounds that snap to one cut yield
+ * equal cuts, and the caller drops them (l5dh_le wants strictly ascending cuts). */
+#define L5DH_LE_MAX 64 /* cuts per call */
+int l5dh_le_cuts(const double* bounds, size_t n, uint32_t* cuts, int64_t* le);
+
+/* Live state.  Under ONE hold of the context lock: staged samples are binned and
+ * pending segments folded; per series i of [first, first+count) the counts at the
+ * ncuts cuts and then the row's count (the `+Inf` bucket, always the last column) go to
+ * le_out[i][0..ncuts] (uint64 [count][ncuts+1]) and the row's exact sum to sums_out[i]
+ * (nullable); then, if series_out is given and/or reset != 0, the per-series snapshot
+ * of the same range is taken from the same state (series_out: count l5dh_summary,
+ * nullable) and the range is cleared -- the buckets, the summaries and the reset all
+ * see exactly the same samples.
+ * accumulate != 0 adds the results to what le_out / sums_out hold (sums_out wraps like
+ * a Java long): a caller keeps lifetime counters across resetting intervals this way.
+ * Every pointer may be host or device memory (cuts included); an accumulating host
+ * output has its old values copied to the device first.
+ * -EINVAL, with nothing written and nothing reset: ncuts outside [1, L5DH_LE_MAX], a cut
+ * outside [1, 1797], cuts not strictly ascending, a bad range, a null cuts / le_out. */
+int l5dh_le(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* cuts, uint32_t ncuts,
+            uint64_t* le_out /* [count][ncuts+1] */, int64_t* sums_out /* [count], nullable */,
+            int accumulate, l5dh_summary* series_out /* nullable */, int reset);
+
+/* The same over external dense rows: counts [n][1798] int32, totals [n] int64 (nullable:
+ * 0) -- the inputs and the domain of l5dh_summarize_dense (every count in [0, 2^31 - 1],
+ * any row sum).  E.g. the g_counts of a rollup: cumulative buckets are linear, so these
+ * are the members' summed buckets. */
+int l5dh_le_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals /* nullable */, size_t n,
+                  const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate);
+
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:
  *  - multi-process (or one thread per context): rank 0 calls l5dh_comm_unique_id,

@@ -41,6 +41,7 @@ PARAM_ROLLUP_ITEM = 14
 
 NO_GROUP = 0xFFFFFFFF  # L5DH_NO_GROUP
 MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
+LE_MAX = 64  # L5DH_LE_MAX
 
 MERGE_REDUCE_SCATTER = 0
 MERGE_ALL_REDUCE = 1
@@ -81,6 +82,9 @@ SIGNATURES = {
     "l5dh_summarize_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp]),
     "l5dh_rollup": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _vp, _vp, _c.c_int]),
     "l5dh_rollup_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _vp]),
+    "l5dh_le_cuts": (_c.c_int, [_vp, _c.c_size_t, _vp, _vp]),
+    "l5dh_le": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int, _vp, _c.c_int]),
+    "l5dh_le_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

@@ -14,6 +14,7 @@
 
 #include "../../include/l5dhist.h"
 #include "l5dh_kernels.hpp"
+#include "l5dh_le.hpp"
 #include "l5dh_merge.hpp"
 #include "l5dh_rollup.hpp"
 
@@ -138,6 +139,7 @@ struct l5dh_ctx {
   bool loopback = false;    // l5dh_comm_init_loopback: the collectives are device copies among the group's contexts
   // label rollups (l5dh_rollup.hip): the staged map, the plan's arrays, the partial rows, staged outputs
   DevBuf ru_group, ru_u32, ru_u64, ru_members, ru_igroup, ru_mlist, ru_partial, ru_tmp, ru_summ, ru_counts, ru_totals;
+  DevBuf le_stage, le_sums_stage;  // cumulative `le` buckets (l5dh_le.hip): staged outputs
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params
@@ -232,6 +234,11 @@ struct StagedOut {
     }
     if (int r = ensure(c, stage, bytes)) return r;
     dev = stage.as<T>();
+    return 0;
+  }
+  // An accumulating output: the caller's old values go to the staging buffer first.
+  int load(l5dh_ctx* c) const {
+    if (staged()) HIPCHK(c, hipMemcpyAsync(dev, user, bytes, hipMemcpyDefault, c->stream));
     return 0;
   }
   // Second half: the copy back to the caller, if staged.

@@ -114,6 +114,26 @@ struct SrcExt {  // external dense rows, stride 1798 int32 (8-B aligned)
   }
 };
 
+// ---- row sources of the per-row kernels over a range or a map (the rollup's accumulate,
+// the cumulative `le` buckets): row i and its exact sum ----
+struct LiveRows {  // state rows of series first + i
+  const uint32_t* __restrict__ counts;
+  const int64_t* __restrict__ total;
+  const int64_t* __restrict__ sumfix;
+  uint32_t first;
+  __device__ __forceinline__ SrcRow32 row(uint32_t i) const { return SrcRow32{counts + (size_t)(first + i) * ROW}; }
+  // (+ sumfix as in k_rows: a one-tile space's fold leaves its escaped samples' sums there)
+  __device__ __forceinline__ uint64_t sum(uint32_t i) const {
+    return (uint64_t)total[first + i] + (uint64_t)sumfix[first + i];
+  }
+};
+struct ExtRows {  // external dense rows [count][1798] (+ totals, nullable)
+  const int32_t* __restrict__ rows;
+  const int64_t* __restrict__ totals;
+  __device__ __forceinline__ SrcExt row(uint32_t i) const { return SrcExt{rows + (size_t)i * NB}; }
+  __device__ __forceinline__ uint64_t sum(uint32_t i) const { return totals ? (uint64_t)totals[i] : 0ull; }
+};
+
 __device__ __forceinline__ uint32_t sum4(uint4 v) { return v.x + v.y + v.z + v.w; }
 // The lane's nine group sums at a width that cannot wrap.  Four legal buckets (each
 // <= 2^31 - 1 in an int32 row, a u32 in a state row) sum to 2^32 and more, but stay below

@@ -548,6 +548,62 @@ int do_rollup(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, c
   return sync_stream(c);
 }
 
+// ---- cumulative `le` buckets -----------------------------------------------------
+// The cuts of a call, on the host and checked: K in [1, LE_MAX], each cut in [1, NL],
+// strictly ascending.  A device array is fetched first (one small copy and wait).
+int le_fetch_cuts(l5dh_ctx* c, const uint32_t* cuts, uint32_t ncuts, LeCuts& out) {
+  if (ncuts < 1 || ncuts > LE_MAX) return fail(c, -EINVAL, "le: ncuts must be in [1, 64]");
+  if (!cuts) return fail(c, -EINVAL, "le: null cuts");
+  memset(&out, 0, sizeof(out));
+  if (is_device_ptr(cuts)) {
+    HIPCHK(c, hipMemcpyAsync(out.c, cuts, (size_t)ncuts * 4, hipMemcpyDeviceToHost, c->stream));
+    if (int r = sync_stream(c)) return r;
+  } else {
+    memcpy(out.c, cuts, (size_t)ncuts * 4);
+  }
+  for (uint32_t k = 0; k < ncuts; ++k) {
+    if (out.c[k] < 1 || out.c[k] > (uint32_t)NL)
+      return fail(c, -EINVAL, "le: cuts[" + std::to_string(k) + "] is outside [1, 1797]");
+    if (k && out.c[k] <= out.c[k - 1])
+      return fail(c, -EINVAL, "le: cuts[" + std::to_string(k) + "] does not ascend strictly");
+  }
+  return 0;
+}
+
+// Cumulative counts at the cuts of the live state rows of series [first, first + count)
+// (ext == nullptr; then also the per-series snapshot / reset of the same state) or of
+// external dense rows ext[count][1798].  The caller holds the lock and has checked the
+// arguments; count > 0.
+int do_le(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const int64_t* ext_totals,
+          const LeCuts& cuts, uint32_t K, uint64_t* le_out, int64_t* sums_out, int accumulate,
+          l5dh_summary* series_out, int reset) {
+  int r;
+  const bool live = ext == nullptr;
+  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
+  StagedOut<uint64_t> le;
+  StagedOut<int64_t> sums;
+  StagedOut<Summary88> s_summ;
+  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_export_state)
+  if ((r = stage_in(c, ext, (size_t)count * NB, 8, c->stage_in_counts)) ||
+      (r = stage_in(c, ext_totals, count, 8, c->stage_in_totals)) ||
+      (r = le.begin(c, le_out, (size_t)count * (K + 1), c->le_stage)) ||
+      (r = sums.begin(c, sums_out, count, c->le_sums_stage)) ||
+      (r = s_summ.begin(c, series_out, count, c->stage_summ)))
+    return r;
+  // (an accumulating host output: its old values are staged in)
+  if (accumulate && ((r = le.load(c)) || (r = sums.load(c)))) return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, launch_le(state(c), first, count, ext, ext_totals, cuts, K, le.dev, sums.dev, accumulate, c->stream));
+    // the per-series snapshot and the reset of the same range, from the same state
+    if (live && (s_summ.dev || reset))
+      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{s_summ.dev, nullptr, first, count, nullptr},
+                            reset, nullptr, c->stream));
+  }
+  if ((r = le.end(c)) || (r = sums.end(c)) || (r = s_summ.end(c))) return r;
+  return sync_stream(c);
+}
+
 }  // namespace
 
 l5dh_ctx::~l5dh_ctx() {
@@ -757,6 +813,32 @@ int l5dh_rollup_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals,
   static const int32_t none = 0;
   return do_rollup(c, 0, (uint32_t)n, n ? counts : &none, n ? totals : nullptr, group, ngroups, g_out, g_counts_out,
                    g_totals_out, nullptr, 0);
+}
+
+int l5dh_le_cuts(const double* bounds, size_t n, uint32_t* cuts, int64_t* le) { return le_cuts(bounds, n, cuts, le); }
+
+int l5dh_le(l5dh_ctx* c, uint32_t first, uint32_t count, const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out,
+            int64_t* sums_out, int accumulate, l5dh_summary* series_out, int reset) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  LeCuts lc;
+  if (int r = le_fetch_cuts(c, cuts, ncuts, lc)) return r;
+  if (count == 0) return 0;
+  if (!le_out) return fail(c, -EINVAL, "le: null output");
+  return do_le(c, first, count, nullptr, nullptr, lc, ncuts, le_out, sums_out, accumulate, series_out, reset);
+}
+
+int l5dh_le_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, size_t n, const uint32_t* cuts,
+                  uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (n > 0xFFFFFFFFull) return fail(c, -EINVAL, "le: more than 2^32 - 1 dense rows");
+  LeCuts lc;
+  if (int r = le_fetch_cuts(c, cuts, ncuts, lc)) return r;
+  if (n == 0) return 0;
+  if (!counts || !le_out) return fail(c, -EINVAL, "le: null dense rows or output");
+  return do_le(c, 0, (uint32_t)n, counts, totals, lc, ncuts, le_out, sums_out, accumulate, nullptr, 0);
 }
 
 int l5dh_peek(l5dh_ctx* c, uint32_t series, l5dh_bucket_count* out, size_t cap, size_t* n_out) {

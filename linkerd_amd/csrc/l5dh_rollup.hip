@@ -33,24 +33,8 @@
 namespace l5dh {
 namespace {
 
-// ---- row sources of the accumulate kernel: member i of the map ----
-struct LiveRows {  // state rows of series first + i
-  const uint32_t* __restrict__ counts;
-  const int64_t* __restrict__ total;
-  const int64_t* __restrict__ sumfix;
-  uint32_t first;
-  __device__ __forceinline__ SrcRow32 row(uint32_t i) const { return SrcRow32{counts + (size_t)(first + i) * ROW}; }
-  // (+ sumfix as in k_rows: a one-tile space's fold leaves its escaped samples' sums there)
-  __device__ __forceinline__ uint64_t sum(uint32_t i) const {
-    return (uint64_t)total[first + i] + (uint64_t)sumfix[first + i];
-  }
-};
-struct ExtRows {  // external dense rows [count][1798] (+ totals, nullable)
-  const int32_t* __restrict__ rows;
-  const int64_t* __restrict__ totals;
-  __device__ __forceinline__ SrcExt row(uint32_t i) const { return SrcExt{rows + (size_t)i * NB}; }
-  __device__ __forceinline__ uint64_t sum(uint32_t i) const { return totals ? (uint64_t)totals[i] : 0ull; }
-};
+// (the row sources of the accumulate kernel, member i of the map: LiveRows / ExtRows of
+// l5dh_device.hpp)
 
 // The group series first + i is a member of, or RU_NO_GROUP.  An invalid entry counts
 // as no group (bad != nullptr: its index is reported).

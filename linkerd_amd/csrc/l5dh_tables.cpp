@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 
 namespace l5dh {
 
@@ -40,6 +41,27 @@ int host_bucket(const int32_t* L, int64_t v) {
     if ((int64_t)L[m] <= v) lo = m + 1; else hi = m;
   }
   return lo;
+}
+
+int le_cuts(const double* bounds, size_t n, uint32_t* cuts, int64_t* le) {
+  const HostLimits& hl = host_limits();
+  if (!hl.ok) return -EIO;
+  if (n && !bounds) return -EINVAL;
+  for (size_t i = 0; i < n; ++i)
+    if (!(bounds[i] >= 0.0)) return -EINVAL;  // (NaN compares false)
+  for (size_t i = 0; i < n; ++i) {
+    const double f = std::floor(bounds[i]);
+    // (int32 limits are exact doubles; f may be +Inf)
+    int lo = 0, hi = NL;  // c = #{ j : L[j] - 1 <= f }
+    while (lo < hi) {
+      const int m = (lo + hi) / 2;
+      if ((double)hl.L[m] - 1.0 <= f) lo = m + 1; else hi = m;
+    }
+    const int c = lo < 1 ? 1 : lo;
+    if (cuts) cuts[i] = (uint32_t)c;
+    if (le) le[i] = (int64_t)hl.L[c - 1] - 1;
+  }
+  return 0;
 }
 
 int build_bucket_lut(const int32_t* L, uint32_t* lut) {

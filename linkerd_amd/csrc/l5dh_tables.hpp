@@ -3,6 +3,7 @@
 // (tests/c/tables_check.cpp runs it under ASan + UBSan against the oracle).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 namespace l5dh {
@@ -28,6 +29,14 @@ const HostLimits& host_limits();
 
 // bucket(v) = number of limits <= v (upper bound), for the LUT builders.
 int host_bucket(const int32_t* L, int64_t v);
+
+// Cumulative `le` buckets.  A cut c in [1, NL] stands for buckets 0..c-1, i.e. the samples
+// with (long)value <= L[c-1] - 1, so its exact label is le = L[c-1] - 1.  Each bound B is
+// snapped DOWN to the largest such le <= floor(B): cuts[i] = #{ j : L[j] - 1 <= floor(B) }
+// clipped to [1, NL] (B < 1 gives cut 1, le 0; +Inf and anything >= L[NL-1] - 1 give NL),
+// le[i] = L[cuts[i] - 1] - 1.  No deduplication: bounds that snap to one cut yield equal
+// cuts.  NaN or B < 0: -EINVAL (nothing is written then).  cuts / le: each nullable.
+int le_cuts(const double* bounds, size_t n, uint32_t* cuts, int64_t* le);
 
 // LUT for bucket_lut: builds lut[LUT_N] from the limits; returns the largest
 // number of limits inside one LUT interval (the device search assumes <= 2).

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 
-_NP_OF_TORCH = {"torch.int32": np.int32, "torch.uint32": np.uint32, "torch.int64": np.int64,
+_NP_OF_TORCH = {"torch.int32": np.int32, "torch.uint32": np.uint32, "torch.int64": np.int64, "torch.uint64": np.uint64,
                 "torch.float32": np.float32, "torch.float64": np.float64, "torch.uint8": np.uint8}
 
 
@@ -305,6 +305,100 @@ class HistogramEngine:
         """The same over external dense rows (counts [n][1798] int32, totals [n] int64 or
         None), e.g. the slice a rank received from ``merge``."""
         return self._rollup_numpy(group, ngroups, with_counts, False, dense=(counts, totals))
+
+    # -- cumulative le buckets ------------------------------------------------------
+    @staticmethod
+    def le_cuts(bounds):
+        """(cuts uint32, le int64) of the requested upper bounds (l5dh_le_cuts): each
+        bound is snapped down to the largest exact label le = L[c-1] - 1 <= floor(bound);
+        bounds that snap to one cut are dropped, and the cuts come back ascending.
+        Cut c counts the samples with (long)value <= le.  +Inf gives cut 1797."""
+        b = np.ascontiguousarray(np.asarray(bounds, np.float64).reshape(-1))
+        cuts, le = np.zeros(b.size, np.uint32), np.zeros(b.size, np.int64)
+        rc = N.load().l5dh_le_cuts(b.ctypes.data, b.size, cuts.ctypes.data, le.ctypes.data)
+        if rc != 0:
+            raise N.L5dhError(rc, "l5dh_le_cuts", "bounds must be >= 0 and not NaN")
+        cuts, keep = np.unique(cuts, return_index=True)
+        return cuts, le[keep]
+
+    @staticmethod
+    def _cuts(cuts):
+        """The uint32 cuts of a call: a torch tensor as it is, anything else as a numpy
+        array (range and order are checked by the library)."""
+        if _is_torch(cuts):
+            return cuts
+        a = np.asarray(cuts).reshape(-1)
+        if a.dtype != np.dtype(np.uint32):
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError(f"cuts: dtype {a.dtype} is not an integer type")
+            if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+                raise ValueError("cuts must fit uint32")
+            a = a.astype(np.uint32)
+        return np.ascontiguousarray(a)
+
+    def le_counts_into(self, cuts, le_out, sums=None, series=None, first: int = 0, count: Optional[int] = None,
+                       reset: bool = False, accumulate: bool = False, dense=None) -> None:
+        """Exact cumulative bucket counts into caller buffers (numpy, or torch tensors on
+        the engine's GPU): le_out uint64 (or int64) [count][K+1] -- per series the counts
+        at the K cuts (``le_cuts``), then the row's count (the +Inf bucket); sums int64
+        [count] the exact sums.  dense=None reads the live rows of series [first,
+        first+count) (l5dh_le; ``series`` then receives the per-series summaries of the
+        same state and ``reset`` clears the range, atomically with the buckets);
+        dense=(counts, totals) reads external dense rows (l5dh_le_dense).  ``accumulate``
+        adds to what the outputs hold: lifetime counters across resetting intervals."""
+        if dense is not None:
+            dcounts, dtotals = dense
+            n = _numel(dcounts) // N.NBUCKETS
+            if n * N.NBUCKETS != _numel(dcounts):
+                raise ValueError("dense counts must hold whole rows of 1798 buckets")
+            if series is not None or reset:
+                raise ValueError("dense rows have no series snapshot and nothing to reset")
+            first, count = 0, n
+        else:
+            first, count = self._range(first, count)
+        cuts = self._cuts(cuts)
+        K = _numel(cuts)
+        kp = self._buf(cuts, (np.uint32, np.int32), "cuts")
+        lp = self._buf(le_out, (np.uint64, np.int64), "le_out", count * (K + 1), writable=True)
+        if le_out is None:
+            raise ValueError("le_out: an output buffer is needed")
+        tp = self._buf(sums, (np.int64,), "sums", count, writable=True)
+        if dense is not None:
+            dcp = self._buf(dcounts, (np.int32,), "dense counts")
+            dtp = self._buf(dtotals, (np.int64,), "dense totals", count)
+            self._check(self._lib.l5dh_le_dense(self._ctx, dcp, dtp, count, kp, K, lp, tp, int(bool(accumulate))),
+                        "l5dh_le_dense")
+            return
+        rp = self._summ_buf(series, count, "series")
+        self._check(self._lib.l5dh_le(self._ctx, first, count, kp, K, lp, tp, int(bool(accumulate)), rp, int(reset)),
+                    "l5dh_le")
+
+    def le_counts(self, cuts, first: int = 0, count: Optional[int] = None, reset: bool = False,
+                  with_series: bool = False, accumulate_into=None):
+        """(le uint64 [count][K+1], sums int64 [count]) of series [first, first+count),
+        followed by the per-series summaries of the same state with ``with_series``;
+        ``reset`` clears the range atomically with both.  accumulate_into=(le, sums): the
+        results are added to these arrays (which are returned) instead of new ones."""
+        first, count = self._range(first, count)
+        K = _numel(self._cuts(cuts))
+        if accumulate_into is not None:
+            le, sums = accumulate_into
+        else:
+            le, sums = np.zeros((count, K + 1), np.uint64), np.zeros(count, np.int64)
+        series = np.zeros(count, dtype=N.SUMMARY_DTYPE) if with_series else None
+        self.le_counts_into(cuts, le, sums, series, first=first, count=count, reset=reset,
+                            accumulate=accumulate_into is not None)
+        return (le, sums, series) if with_series else (le, sums)
+
+    def le_counts_dense(self, counts, totals, cuts):
+        """The same over external dense rows (counts [n][1798] int32, totals [n] int64 or
+        None), e.g. the g_counts of a rollup: cumulative buckets are linear, so these are
+        the members' summed buckets."""
+        n = _numel(counts) // N.NBUCKETS
+        K = _numel(self._cuts(cuts))
+        le, sums = np.zeros((n, K + 1), np.uint64), np.zeros(n, np.int64)
+        self.le_counts_into(cuts, le, sums, dense=(counts, totals))
+        return le, sums
 
     # -- fleet merge (RCCL) ------------------------------------------------------
     @staticmethod

@@ -86,16 +86,43 @@ def write_metrics(tree: MetricsTree, out: List[str], prefix0: Tuple[str, ...] = 
         write_metrics(child, out, prefix1 + (name,), labels1)
 
 
+def write_histogram_metrics(tree: MetricsTree, engine, out: List[str], prefix0: Tuple[str, ...] = (),
+                            labels0: Labels = ()) -> None:
+    """Prometheus histogram lines of every live Stat from the lifetime cumulative buckets
+    of ``engine`` (a StatEngine after enable_le): ``{key}_hist_bucket{..., le="<le>"}`` per
+    cut, then ``le="+Inf"``, ``{key}_hist_sum`` and ``{key}_hist_count``.  Counters that
+    only grow, so the server can sum and divide them (sum by (le), histogram_quantile);
+    the ``_hist`` infix keeps them apart from the summary's per-interval _count / _sum.
+    Keys, labels and escaping are write_metrics'; each le is the exact snapped label."""
+    prefix1, labels1 = _rewrite(prefix0, labels0)
+    m = tree.metric
+    if isinstance(m, Metric.Stat) and m.series_id is not None and engine.le_cuts is not None:
+        key = escape_key(":".join(prefix1))
+        row = engine.le_buckets[m.series_id]
+        for le, n in zip(engine.le_labels, row[:-1]):
+            lab = format_labels(labels1 + (("le", long_to_string(int(le))),))
+            out.append(f"{key}_hist_bucket{lab} {long_to_string(int(n))}\n")
+        out.append(f"{key}_hist_bucket{format_labels(labels1 + (('le', '+Inf'),))} {long_to_string(int(row[-1]))}\n")
+        lab = format_labels(labels1)
+        out.append(f"{key}_hist_sum{lab} {long_to_string(int(engine.le_sums[m.series_id]))}\n")
+        out.append(f"{key}_hist_count{lab} {long_to_string(int(row[-1]))}\n")
+    for name, child in tree.children.items():
+        write_histogram_metrics(child, engine, out, prefix1 + (name,), labels1)
+
+
 class PrometheusTelemeter:
     """PrometheusTelemeter (PrometheusTelemeter.scala:17-35): /admin/metrics/prometheus."""
 
     path = "/admin/metrics/prometheus"
 
-    def __init__(self, metrics: MetricsTree, rollups=None):
+    def __init__(self, metrics: MetricsTree, rollups=None, histograms=None):
         self.metrics = metrics
         # optional (RollupPlan, group summaries) pair of linkerd_amd.rollup, settable
         # later: its lines follow the tree's
         self.rollups = rollups
+        # optional StatEngine with enable_le, settable later: the Stats' cumulative
+        # `le` bucket lines (write_histogram_metrics) follow the tree's and the rollups'
+        self.histograms = histograms
 
     def render(self) -> str:
         out: List[str] = []
@@ -104,6 +131,8 @@ class PrometheusTelemeter:
             from .rollup import write_rollup_metrics
             plan, summaries = self.rollups
             write_rollup_metrics(plan, summaries, out)
+        if self.histograms is not None:
+            write_histogram_metrics(self.metrics, self.histograms, out)
         return "".join(out)
 
 

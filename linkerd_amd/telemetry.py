@@ -77,6 +77,11 @@ class StatEngine:
         self._limits = None
         self._tls = threading.local()
         self._buffers: List["_Staging"] = []
+        # lifetime cumulative buckets (enable_le): cuts, their exact labels, the counters
+        self.le_cuts: Optional[np.ndarray] = None
+        self.le_labels: Optional[np.ndarray] = None
+        self.le_buckets: Optional[np.ndarray] = None
+        self.le_sums: Optional[np.ndarray] = None
 
     # registry (MetricsTree.mkStat assigns the id; MetricsTree.prune releases it)
     def register(self) -> int:
@@ -95,6 +100,9 @@ class StatEngine:
         on the GPU before the id can be handed out again, so a new Stat starts empty."""
         self.flush()
         self.engine.snapshot(first=sid, count=1, reset=True)
+        if self.le_cuts is not None:  # the id's lifetime buckets end with its Stat
+            self.le_buckets[sid] = 0
+            self.le_sums[sid] = 0
         with self._lock:
             self._free.append(sid)
 
@@ -171,6 +179,32 @@ class StatEngine:
         groups, series = self.engine.rollup(group_of, ngroups, first=0, count=self.capacity, reset=reset,
                                             with_series=True)
         return series, groups
+
+    # cumulative `le` buckets (Prometheus histogram counters)
+    def enable_le(self, bounds) -> None:
+        """Keep lifetime cumulative bucket counters at ``bounds`` (snapped down to exact
+        labels and deduplicated: HistogramEngine.le_cuts): le_buckets uint64
+        [capacity][K+1] -- the K cuts, then +Inf -- and le_sums int64 [capacity], fed by
+        snapshot_all_le.  Calling it again starts the counters anew."""
+        cuts, labels = self.engine.le_cuts(bounds)
+        if not 1 <= len(cuts) <= 64:
+            raise ValueError(f"enable_le: {len(cuts)} distinct cuts, 1..64 are supported")
+        self.le_cuts, self.le_labels = cuts, labels
+        self.le_buckets = np.zeros((self.capacity, len(cuts) + 1), np.uint64)
+        self.le_sums = np.zeros(self.capacity, np.int64)
+
+    def snapshot_all_le(self, reset: bool = True) -> np.ndarray:
+        """snapshot_all plus the interval's cumulative buckets, from ONE engine call that
+        adds them to the lifetime counters: the buckets, the summaries and the reset see
+        exactly the same samples.  reset=False only looks: the counters stay as they are
+        (the same samples would be added again by the next call)."""
+        if self.le_cuts is None:
+            raise RuntimeError("snapshot_all_le needs enable_le(bounds) first")
+        self.flush()
+        if not reset:
+            return self.engine.snapshot(first=0, count=self.capacity, reset=False)
+        return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True, with_series=True,
+                                     accumulate_into=(self.le_buckets, self.le_sums))[2]
 
 
 class _Staging:
@@ -420,6 +454,21 @@ def snapshot_histograms(tree: MetricsTree, engine: StatEngine) -> int:
     Returns the number of Stats updated."""
     now = time.time()
     summaries = engine.snapshot_all(reset=True)
+    n = 0
+    for _, t in tree.walk():
+        m = t.metric
+        if isinstance(m, Metric.Stat) and m.series_id is not None:
+            m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
+            n += 1
+    return n
+
+
+def snapshot_histograms_le(tree: MetricsTree, engine: StatEngine) -> int:
+    """snapshot_histograms plus the cumulative `le` buckets: the same fused snapshot +
+    reset, whose interval is also added to the engine's lifetime bucket counters
+    (StatEngine.enable_le) by the same engine call.  Returns the number of Stats updated."""
+    now = time.time()
+    summaries = engine.snapshot_all_le(reset=True)
     n = 0
     for _, t in tree.walk():
         m = t.metric

@@ -8,7 +8,7 @@ N=$1; shift
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -w -DL5DH_DEV $*"
 T=$(mktemp -d)
 mkdir -p ../lib_ab
-for f in l5dh_ingest.hip l5dh_snapshot.hip l5dh_merge.hip l5dh_rollup.hip l5dh_engine.cpp l5dh_fleet.cpp l5dh_tables.cpp; do
+for f in l5dh_ingest.hip l5dh_snapshot.hip l5dh_merge.hip l5dh_rollup.hip l5dh_le.hip l5dh_engine.cpp l5dh_fleet.cpp l5dh_tables.cpp; do
   /opt/rocm/bin/hipcc $F -x hip -c $f -o $T/${f%.*}.o &
 done
 wait
