@@ -364,19 +364,36 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 // profiles/r04r_ab.txt, r04s_ab.txt).  A run that does not fit is dropped and flagged; pass 1 (the redo) exits unless k_rfix1 asked for it and adds nothing to
 // sumfix or the error counter.
 //
-// Direct value sums: u64 per direct series in LDS, added to sumfix by each workgroup at
-// the end of its slab.
+// Direct value sums: u32 per direct series in LDS (DS = uint32_t; u64, the earlier layout
+// and twice the LDS, behind variant bit 3), added to sumfix by each workgroup at the end
+// of its slab.  A u32 sum cannot wrap:
+//  - only payloads below DSUM_PMAX = 2^17 are added to it.  The ranking loop's fast test
+//    is f < 2^17 instead of f < V_ESC (the same compare, another constant), so a larger
+//    value takes the escapes' slow path, where a direct series' payload in [2^17, V_ESC)
+//    goes to sumfix with a 64-bit global atomic.  (A per-slot mask of such payloads,
+//    tested after each group, cost level 1 +0.07 ms on C3; an atomic under a per-slot
+//    branch +0.1 ms: profiles/r07_level1_u32_sums_ab.txt.)  Limit: a batch with many values
+//    >= 2^17 pays the slow path for each, direct or not, as one with many >= V_ESC does;
+//  - the thread that owns a direct half-bin keeps A, the bin's records since its sums
+//    were last flushed (dacc, LDS).  After B1 it adds the sub-chunk's count, and once
+//    A > CH 16 lanes of its wave move the bin's 16 sums to sumfix and clear them --
+//    between B1 and B2, where no add is in flight.  (One thread flushing its 16 sums in
+//    turn held B1b up: level 1 +0.1 ms.)  So every sum is <= CH (2^17 - 1) when a
+//    sub-chunk's ranking starts, the sub-chunk adds at most CH (2^17 - 1) more, and
+//    2 CH (2^17 - 1) < 2^32 (the static_assert in the kernel).
 //
 // No LDS atomic of the ranking loop is under a branch that its return value or a
 // uniform flag decides: the compiler then waits for each return before the next slot
 // (s_waitcnt lgkmcnt(0) after every atomic).  Unconditional rank atomics and return-less
-// u64 value sums keep a group's 8 atomics in flight together: bin1 3.56 -> 3.36 ms on C3
+// value sums keep a group's 8 atomics in flight together: bin1 3.56 -> 3.36 ms on C3
 // (profiles/r05k_level1_atomics_ab.txt).  16 K-slot sub-chunks (16 slots per thread)
-// leave the VGPRs for that (24 K spills the prefetch: 3.94 ms) and the LDS for the u64 sums.
+// leave the VGPRs for that (24 K spills the prefetch: 3.94 ms).
 //
 // LDS (u32 words): stage[CH], cnt[1024], offr[1024] {offset | run rank << 16},
 // rdelta[1024], heads[CH / 32], gpre[CH / 64] (u16), direct words [1024] uint2,
-// lut2 [1024] uint2, direct sums [255 x 32] u64.
+// lut2 [1024] uint2, direct sums [255 x 32] DS, and with u32 sums dacc[1024] and breg[1024]
+// uint2 (each thread's bin's region {base, capacity}: two registers with u64 sums, whose
+// LDS is full -- the u32 kernel's few rare-path registers come out of these).
 #ifdef L5DH_PHASES  // development (tools/mk_var.sh, tools/time_lib.py): per-workgroup phase times
 __device__ unsigned long long g_phase1[1024 * 8];
 __device__ unsigned long long g_phase3[1024 * 8];  // level 2
@@ -402,17 +419,20 @@ __device__ unsigned long long g_phase3[1024 * 8];  // level 2
 // (nontemporal batch loads measured slower: bin2 +0.04 ms, round 5)
 __device__ __forceinline__ uint4 ld_stream(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
 constexpr int CHW = 16384;
-using dsum_t = unsigned long long;
+constexpr uint32_t DSUM_PMAX = 1u << 17;  // a u32 direct sum takes payloads below this
+static_assert(DSUM_PMAX == 1u << 17, "the ranking loop tests the bits of 2^17f, 0x48000000");
 // rdelta of a dropped run: a valid delta (run base - stage offset) lies in (-CHW, cap16),
 // cap16 < 2^32 - CHW - 1, so -(CHW + 1) never is one (0xFFFFFFFF is: base 0 at offset 1)
 constexpr uint32_t NODEST = 0xFFFFFFFFu - (uint32_t)CHW;
 constexpr int NT1 = 1024;  // 16 slots per thread
 constexpr int DSUM_N = DIRECT_MAX * TILE;
-constexpr size_t rbin1w_lds() {
-  return (size_t)CHW * 4 + BIN1_BINS * 12 + CHW / 8 + CHW / 32 + 1024 * 8 + LUT2_N * 8 + DSUM_N * sizeof(dsum_t);
+constexpr size_t rbin1w_lds(size_t dsz) {
+  return (size_t)CHW * 4 + BIN1_BINS * 12 + CHW / 8 + CHW / 32 + 1024 * 8 + LUT2_N * 8 + DSUM_N * dsz +
+         (dsz == 4 ? (size_t)BIN1_BINS * 12 : 0);
 }
+static_assert(rbin1w_lds(4) <= 160 * 1024 && rbin1w_lds(8) <= 160 * 1024, "one workgroup's LDS");
 
-template <int NT, int CH>
+template <int NT, int CH, typename DS>
 __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ series, const float* __restrict__ values,
                                                   size_t n, size_t per, uint32_t S, uint32_t F, Tables tb,
                                                   uint32_t* __restrict__ meta, uint32_t* __restrict__ rec32,
@@ -422,6 +442,9 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
   constexpr int PH = PT / 2;
   constexpr int GS = 4;  // slots per group (a group's LDS lookups go out together)
   static_assert(PH % 4 == 0 && PH % GS == 0 && GS % 4 == 0 && CH <= 32768, "halves of whole 16-B groups; 15-bit ranks");
+  constexpr bool S32 = sizeof(DS) == 4;
+  static_assert(!S32 || (2ull * CH * (DSUM_PMAX - 1) < (1ull << 32) && CH <= CHW),
+                "u32 direct sums: <= CH (2^17 - 1) at a sub-chunk's start + as much from the sub-chunk");
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* stage = smem;                                        // [CH] records, sorted by bin
   uint32_t* cnt = stage + CH;                                    // [BIN1_BINS]
@@ -432,7 +455,9 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
   uint2* dw = reinterpret_cast<uint2*>(gpre + CH / 64);          // [1024] {direct bits, direct tiles before}
   uint2* lut2 = dw + 1024;                                       // [LUT2_N]
   __shared__ uint32_t wsum[NT / 64];
-  dsum_t* dsum = reinterpret_cast<dsum_t*>(lut2 + LUT2_N);       // [DSUM_N] direct series value sums
+  DS* dsum = reinterpret_cast<DS*>(lut2 + LUT2_N);               // [DSUM_N] direct series value sums
+  uint32_t* dacc = reinterpret_cast<uint32_t*>(dsum + DSUM_N);   // [BIN1_BINS] (u32 sums) records since a bin's flush
+  uint2* breg = reinterpret_cast<uint2*>(dacc + BIN1_BINS);      // [BIN1_BINS] (u32 sums) region {base, capacity}
   const MetaLayout L = meta_layout(F);
   uint32_t* hdr = meta + L.hdr();
   if (pass == 1 && __builtin_amdgcn_readfirstlane(hdr[H_REDO1]) == 0u) return;
@@ -446,7 +471,10 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
   const int lane = lane_id();
   const int wv = threadIdx.x >> 6;
   for (uint32_t w = threadIdx.x; w < NW; w += NT) dw[w] = make_uint2(meta[L.dbits() + w], meta[L.dpre() + w]);
-  for (uint32_t b = threadIdx.x; b < BIN1_BINS; b += NT) cnt[b] = 0;
+  for (uint32_t b = threadIdx.x; b < BIN1_BINS; b += NT) {
+    cnt[b] = 0;
+    if (S32) dacc[b] = 0;
+  }
   for (uint32_t i = threadIdx.x; i < LUT2_N; i += NT) lut2[i] = tb.lut2[i];
   for (uint32_t i = threadIdx.x; i < ND * TILE; i += NT) dsum[i] = 0;
   __syncthreads();
@@ -462,6 +490,7 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
     const uint32_t b = threadIdx.x + (uint32_t)j * NT;
     my_base[j] = b < TB ? bbase[b] : 0u;
     my_cap[j] = b < TB ? bcap[b] : 0u;
+    if (S32) breg[b] = make_uint2(my_base[j], my_cap[j]);  // (read back by this thread alone)
   }
   PH_INIT
   // the next sub-chunk's first half loaded during this one's scatter / write-out
@@ -540,9 +569,10 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
 #pragma unroll
         for (int q = 0; q < GS; ++q) {
           // fast: +0 <= f < V_ESC, one integer compare of the bit pattern (-0, NaN and
-          // (-1, 0) take the exact slow path, which also truncates them to 0)
+          // (-1, 0) take the exact slow path, which also truncates them to 0); with u32 sums
+          // f < DSUM_PMAX, so that the slow path sees the few payloads the sums must not take
           const float f = fv[g + q];
-          const bool fast = __float_as_uint(f) < 0x49FFC000u;  // bits of (float)V_ESC
+          const bool fast = __float_as_uint(f) < (S32 ? 0x48000000u : 0x49FFC000u);  // bits of 2^17 / (float)V_ESC
           pl[q] = fast ? (uint32_t)f : 0u;
           escm |= (!fast && sv[g + q] < S) ? (1u << q) : 0u;
           if (full) bad |= sv[g + q] >= S;
@@ -557,7 +587,14 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
           for (int q = 0; q < GS; ++q) {
             if ((escm >> q) & 1u) {
               const uint32_t i = cl + 4u * ((uint32_t)(h * (PH / 4) + (g + q) / 4) * NT + threadIdx.x) + (uint32_t)(q & 3);
-              const uint32_t r = payload1_slow(series[i], values[i], tb, pass == 0 ? sumfix : nullptr);
+              const uint32_t si = series[i];
+              const uint32_t r = payload1_slow(si, values[i], tb, pass == 0 ? sumfix : nullptr);
+              if (S32 && pass == 0 && r - DSUM_PMAX < V_ESC - DSUM_PMAX) {
+                // not escaped, but too large for a u32 sum: a direct series' value goes to sumfix here
+                const uint2 d = dw[(si >> (TILE_SHIFT + 5)) & 1023u];
+                if ((d.x >> ((si >> TILE_SHIFT) & 31u)) & 1u)
+                  atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[si]), (unsigned long long)r);
+              }
 #pragma unroll
               for (int u = 0; u < GS; ++u) pl[u] = q == u ? r : pl[u];
             }
@@ -587,8 +624,12 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
           const uint32_t dbin = FS + 2u * di + ((s >> 4) & 1u);
           const uint32_t bn = sel_u32(s < S, sel_u32(direct, dbin, s >> ST_SHIFT), TB);
           pk[h * PH + g + q] = atomicAdd(cnt + bn, 1u) | (bn << 15);
-          // the direct series' value sum (u64: no wrap to check, so nothing reads the return)
-          if (direct && !esc && pass == 0 && p) atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], (dsum_t)p);
+          // the direct series' value sum (no wrap to check -- see above -- so nothing reads the return)
+          if (S32) {  // 0 < p < DSUM_PMAX (so not escaped) in one compare
+            if (direct && pass == 0 && p - 1u < DSUM_PMAX - 1u) atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], (DS)p);
+          } else if (direct && !esc && pass == 0 && p) {
+            atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], (DS)p);
+          }
         }
         // slots 4 (kk NT + thread) + q of the 16-B group kk, as loaded
 #pragma unroll
@@ -603,20 +644,50 @@ __global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ seri
     // run reservations: thread t -> bins t, t + NT, ... (the trash bin TB gets none)
     constexpr int RB = (BIN1_BINS + NT - 1) / NT;
     uint32_t rn[RB], rold[RB], rbase[RB], rcapv[RB];
+    // (u32 sums: this phase's per-thread addresses are computed here, once per sub-chunk, not
+    // hoisted out of the sub-chunk loop into registers the ranking needs)
+    uint32_t tq = threadIdx.x;
+    if (S32) asm volatile("" : "+v"(tq));
 #pragma unroll
     for (int j = 0; j < RB; ++j) {
-      const uint32_t rb_bin = threadIdx.x + (uint32_t)j * NT;
+      const uint32_t rb_bin = tq + (uint32_t)j * NT;
       rn[j] = rb_bin <= TB ? cnt[rb_bin] : 0u;  // records of the bin in this sub-chunk
       rold[j] = 0;
-      rbase[j] = my_base[j];
-      rcapv[j] = my_cap[j];
+      if (S32) {
+        const uint2 r = breg[rb_bin];
+        rbase[j] = r.x;
+        rcapv[j] = r.y;
+      } else {
+        rbase[j] = my_base[j];
+        rcapv[j] = my_cap[j];
+      }
       if (rb_bin < TB && rn[j]) rold[j] = atomicAdd(&bcnt[rb_bin], rn[j]);
+    }
+    if (S32 && pass == 0) {
+      // the u32 sums' guard (no add is in flight here): this direct half-bin's records since its
+      // flush; a bin over the bound is flushed by 16 lanes of its owner's wave, one sum each
+      bool fl = false;
+      if (tq >= FS && tq < TB && rn[0]) {
+        const uint32_t A = dacc[tq] + rn[0];
+        fl = A > (uint32_t)CH;
+        dacc[tq] = fl ? 0u : A;
+      }
+      for (uint64_t fm = __ballot(fl); fm; fm &= fm - 1) {  // (wave-uniform, rarely non-zero)
+        const uint32_t fb = (tq & ~63u) + (uint32_t)__builtin_ctzll(fm) - FS;  // direct half-bin
+        if ((tq & 63u) < TILE / 2) {
+          const uint32_t h = fb * (TILE / 2) + (tq & 63u);  // = di * TILE + series in tile
+          const uint32_t v = (uint32_t)dsum[h];
+          dsum[h] = 0;
+          const uint32_t sr = meta[L.dlist() + h / TILE] * TILE + (h & (TILE - 1));
+          if (v && sr < S) atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[sr]), (unsigned long long)v);
+        }
+      }
     }
     {  // stage offsets and run ranks: a block scan of {count, non-empty} (one bin per thread), run heads
       static_assert(NT == BIN1_BINS && RB == 1, "one bin per thread");
       const uint32_t pv = rn[0] | ((rn[0] ? 1u : 0u) << 16);  // (counts sum to <= CH < 2^16: no carry)
       const uint32_t wi = wave_incl_scan32(pv);
-      if (lane == 63) wsum[wv] = wi;
+      if ((tq & 63u) == 63u) wsum[tq >> 6] = wi;
       __syncthreads();  // B1b: wave totals
       uint32_t pre = 0;
       for (int q = 0; q < wv; ++q) pre += wsum[q];
@@ -1311,12 +1382,15 @@ hipError_t launch_fetch_host(const uint32_t* hs, const uint32_t* hv, uint32_t* d
 
 hipError_t set_ingest_attributes() {
   hipError_t e;
+  if ((e = hipFuncSetAttribute((const void*)k_rbin1w<NT1, CHW, unsigned long long>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbin1w_lds(8))))
+    return e;
   if ((e = hipFuncSetAttribute((const void*)k_rsample, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4)))
     return e;
   if ((e = hipFuncSetAttribute((const void*)k_rplan1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RPLAN1_LDS)))
     return e;
-  return hipFuncSetAttribute((const void*)k_rbin1w<NT1, CHW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)rbin1w_lds());
+  return hipFuncSetAttribute((const void*)k_rbin1w<NT1, CHW, uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)rbin1w_lds(4));
 }
 
 hipError_t launch_ingest(const IngestArgs& a, int stage, hipStream_t st) {
@@ -1335,8 +1409,14 @@ hipError_t launch_ingest(const IngestArgs& a, int stage, hipStream_t st) {
       break;
     case 1:  // level 1, its fix-up, the redo pass (exits at once unless needed)
       for (int pass = 0; pass < 2; ++pass) {
-        hipLaunchKernelGGL((k_rbin1w<NT1, CHW>), dim3(a.G), dim3(NT1), rbin1w_lds(), st, a.series, a.values, a.n,
-                           a.per, a.S, a.F, a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err, a.vec ? 1 : 0, pass);
+        if (a.dsum64)
+          hipLaunchKernelGGL((k_rbin1w<NT1, CHW, unsigned long long>), dim3(a.G), dim3(NT1), rbin1w_lds(8), st, a.series,
+                             a.values, a.n, a.per, a.S, a.F, a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err,
+                             a.vec ? 1 : 0, pass);
+        else
+          hipLaunchKernelGGL((k_rbin1w<NT1, CHW, uint32_t>), dim3(a.G), dim3(NT1), rbin1w_lds(4), st, a.series,
+                             a.values, a.n, a.per, a.S, a.F, a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err,
+                             a.vec ? 1 : 0, pass);
         if (pass == 0) hipLaunchKernelGGL(k_rfix1, dim3(1), dim3(1024), 0, st, a.F, a.meta, a.err, a.err_host);
       }
       break;
