@@ -82,7 +82,6 @@ enum {
                                   every variant computes the same results; bit 0: one-tile folds in u16 bins;
                                   bit 1: DMA copies of pinned host batches; bit 2: every ingest batch's
                                   capacity plan made as for a first interval, from its sample alone;
-                                  bit 3: level 1's direct value sums in u64 LDS words;
                                   other bits are ignored) */
 };
 

@@ -343,7 +343,6 @@ int do_ingest(l5dh_ctx* c, const uint32_t* series, const float* values, size_t n
   a.dmax = std::min<uint32_t>(c->direct_max, ((uint32_t)BIN1_BINS - 9 - FS) / 2);
   a.pct = c->region_pct;
   a.vec = vec;
-  a.dsum64 = (c->variant & 8) != 0;
   {
     KTimer kt(c, L5DH_K_SCAN);
     // variant bit 2 (measurement): forget the previous batch's exact key counts, so every

@@ -343,9 +343,6 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
   RP_MARK(6)
 }
 
-
-
-
 // ------------------------------------------------------------------------
 // Level 1, one 1024-thread workgroup per CU walking its slab in 16K-slot sub-chunks.
 // Bins: the FS super-tiles (u32 records with the value, for level 2), two half-bins
@@ -364,9 +361,8 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 // profiles/r04r_ab.txt, r04s_ab.txt).  A run that does not fit is dropped and flagged; pass 1 (the redo) exits unless k_rfix1 asked for it and adds nothing to
 // sumfix or the error counter.
 //
-// Direct value sums: u32 per direct series in LDS (DS = uint32_t; u64, the earlier layout
-// and twice the LDS, behind variant bit 3), added to sumfix by each workgroup at the end
-// of its slab.  A u32 sum cannot wrap:
+// Direct value sums: u32 per direct series in LDS, added to sumfix by each workgroup at
+// the end of its slab.  A u32 sum cannot wrap:
 //  - only payloads below DSUM_PMAX = 2^17 are added to it.  The ranking loop's fast test
 //    is f < 2^17 instead of f < V_ESC (the same compare, another constant), so a larger
 //    value takes the escapes' slow path, where a direct series' payload in [2^17, V_ESC)
@@ -376,11 +372,11 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 //    >= 2^17 pays the slow path for each, direct or not, as one with many >= V_ESC does;
 //  - the thread that owns a direct half-bin keeps A, the bin's records since its sums
 //    were last flushed (dacc, LDS).  After B1 it adds the sub-chunk's count, and once
-//    A > CH 16 lanes of its wave move the bin's 16 sums to sumfix and clear them --
+//    A > CHW 16 lanes of its wave move the bin's 16 sums to sumfix and clear them --
 //    between B1 and B2, where no add is in flight.  (One thread flushing its 16 sums in
-//    turn held B1b up: level 1 +0.1 ms.)  So every sum is <= CH (2^17 - 1) when a
-//    sub-chunk's ranking starts, the sub-chunk adds at most CH (2^17 - 1) more, and
-//    2 CH (2^17 - 1) < 2^32 (the static_assert in the kernel).
+//    turn held B1b up: level 1 +0.1 ms.)  So every sum is <= CHW (2^17 - 1) when a
+//    sub-chunk's ranking starts, the sub-chunk adds at most CHW (2^17 - 1) more, and
+//    2 CHW (2^17 - 1) < 2^32 (the static_assert with Bin1Lds).
 //
 // No LDS atomic of the ranking loop is under a branch that its return value or a
 // uniform flag decides: the compiler then waits for each return before the next slot
@@ -389,11 +385,7 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 // (profiles/r05k_level1_atomics_ab.txt).  16 K-slot sub-chunks (16 slots per thread)
 // leave the VGPRs for that (24 K spills the prefetch: 3.94 ms).
 //
-// LDS (u32 words): stage[CH], cnt[1024], offr[1024] {offset | run rank << 16},
-// rdelta[1024], heads[CH / 32], gpre[CH / 64] (u16), direct words [1024] uint2,
-// lut2 [1024] uint2, direct sums [255 x 32] DS, and with u32 sums dacc[1024] and breg[1024]
-// uint2 (each thread's bin's region {base, capacity}: two registers with u64 sums, whose
-// LDS is full -- the u32 kernel's few rare-path registers come out of these).
+// LDS: Bin1Lds below, the one definition of the arrays, their order and their sizes.
 #ifdef L5DH_PHASES  // development (tools/mk_var.sh, tools/time_lib.py): per-workgroup phase times
 __device__ unsigned long long g_phase1[1024 * 8];
 __device__ unsigned long long g_phase3[1024 * 8];  // level 2
@@ -418,361 +410,497 @@ __device__ unsigned long long g_phase3[1024 * 8];  // level 2
 #endif
 // (nontemporal batch loads measured slower: bin2 +0.04 ms, round 5)
 __device__ __forceinline__ uint4 ld_stream(const uint32_t* p) { return *reinterpret_cast<const uint4*>(p); }
-constexpr int CHW = 16384;
+constexpr int CHW = 16384;  // slots per sub-chunk
+constexpr int NT1 = 1024;   // 16 slots per thread
+constexpr int B1_PT = CHW / NT1;  // slots per thread, loaded and ranked in halves
+constexpr int B1_PH = B1_PT / 2;
+constexpr int B1_GS = 4;          // slots per group (a group's LDS lookups go out together)
+constexpr int B1_HG = B1_PH / 4;  // 16-B groups per half and array
+static_assert(B1_PH % 4 == 0 && B1_PH % B1_GS == 0 && B1_GS % 4 == 0, "halves of whole 16-B groups");
+static_assert(NT1 == BIN1_BINS, "one bin per thread");
 constexpr uint32_t DSUM_PMAX = 1u << 17;  // a u32 direct sum takes payloads below this
 static_assert(DSUM_PMAX == 1u << 17, "the ranking loop tests the bits of 2^17f, 0x48000000");
 // rdelta of a dropped run: a valid delta (run base - stage offset) lies in (-CHW, cap16),
 // cap16 < 2^32 - CHW - 1, so -(CHW + 1) never is one (0xFFFFFFFF is: base 0 at offset 1)
 constexpr uint32_t NODEST = 0xFFFFFFFFu - (uint32_t)CHW;
-constexpr int NT1 = 1024;  // 16 slots per thread
 constexpr int DSUM_N = DIRECT_MAX * TILE;
-constexpr size_t rbin1w_lds(size_t dsz) {
-  return (size_t)CHW * 4 + BIN1_BINS * 12 + CHW / 8 + CHW / 32 + 1024 * 8 + LUT2_N * 8 + DSUM_N * dsz +
-         (dsz == 4 ? (size_t)BIN1_BINS * 12 : 0);
-}
-static_assert(rbin1w_lds(4) <= 160 * 1024 && rbin1w_lds(8) <= 160 * 1024, "one workgroup's LDS");
 
-template <int NT, int CH, typename DS>
-__global__ __launch_bounds__(NT) void k_rbin1w(const uint32_t* __restrict__ series, const float* __restrict__ values,
-                                                  size_t n, size_t per, uint32_t S, uint32_t F, Tables tb,
-                                                  uint32_t* __restrict__ meta, uint32_t* __restrict__ rec32,
-                                                  uint16_t* __restrict__ rec16, int64_t* __restrict__ sumfix,
-                                                  uint32_t* __restrict__ err, int vec, int pass) {
-  constexpr int PT = CH / NT;  // slots per thread, loaded and ranked in halves
-  constexpr int PH = PT / 2;
-  constexpr int GS = 4;  // slots per group (a group's LDS lookups go out together)
-  static_assert(PH % 4 == 0 && PH % GS == 0 && GS % 4 == 0 && CH <= 32768, "halves of whole 16-B groups; 15-bit ranks");
-  constexpr bool S32 = sizeof(DS) == 4;
-  static_assert(!S32 || (2ull * CH * (DSUM_PMAX - 1) < (1ull << 32) && CH <= CHW),
-                "u32 direct sums: <= CH (2^17 - 1) at a sub-chunk's start + as much from the sub-chunk");
+// k_rbin1w's dynamic LDS: byte offsets in layout order, each array's size in the next
+// line's sum, and typed views of them.  (wsum, the block scan's 16 wave totals, is a
+// static array of the kernel.)
+struct Bin1Lds {
+  static constexpr int DW_N = 1024;  // direct-bitmap words: 32 tiles each, F <= 32768
+  static constexpr size_t o_stage = 0;                           // u32 [CHW] records: in slot order, then sorted by bin
+  static constexpr size_t o_cnt = o_stage + CHW * 4;             // u32 [BIN1_BINS] records per bin
+  static constexpr size_t o_offr = o_cnt + BIN1_BINS * 4;        // u32 [BIN1_BINS] by bin: stage offset | run rank << 16
+  static constexpr size_t o_rdelta = o_offr + BIN1_BINS * 4;     // u32 [BIN1_BINS] by run rank
+  static constexpr size_t o_heads = o_rdelta + BIN1_BINS * 4;    // u32 [CHW / 32] run-head bitmap of the stage
+  static constexpr size_t o_gpre = o_heads + CHW / 32 * 4;       // u16 [CHW / 64] runs before each 64-entry group
+  static constexpr size_t o_dw = o_gpre + CHW / 64 * 2;          // uint2 [DW_N] {direct bits, direct tiles before}
+  static constexpr size_t o_lut2 = o_dw + DW_N * 8;              // uint2 [LUT2_N]
+  static constexpr size_t o_dsum = o_lut2 + LUT2_N * 8;          // u32 [DSUM_N] direct series' value sums
+  static constexpr size_t o_dacc = o_dsum + DSUM_N * 4;          // u32 [BIN1_BINS] records since a bin's sums were flushed
+  static constexpr size_t o_breg = o_dacc + BIN1_BINS * 4;       // uint2 [BIN1_BINS] each bin's region {base, capacity}
+  static constexpr size_t bytes = o_breg + BIN1_BINS * 8;
+
+  template <typename T>
+  static __device__ __forceinline__ T* at(uint32_t* smem, size_t o) {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(smem) + o);
+  }
+  static __device__ __forceinline__ uint32_t* stage(uint32_t* smem) { return at<uint32_t>(smem, o_stage); }
+  static __device__ __forceinline__ uint32_t* cnt(uint32_t* smem) { return at<uint32_t>(smem, o_cnt); }
+  static __device__ __forceinline__ uint32_t* offr(uint32_t* smem) { return at<uint32_t>(smem, o_offr); }
+  static __device__ __forceinline__ uint32_t* rdelta(uint32_t* smem) { return at<uint32_t>(smem, o_rdelta); }
+  static __device__ __forceinline__ uint32_t* heads(uint32_t* smem) { return at<uint32_t>(smem, o_heads); }
+  static __device__ __forceinline__ uint16_t* gpre(uint32_t* smem) { return at<uint16_t>(smem, o_gpre); }
+  static __device__ __forceinline__ uint2* dw(uint32_t* smem) { return at<uint2>(smem, o_dw); }
+  static __device__ __forceinline__ uint2* lut2(uint32_t* smem) { return at<uint2>(smem, o_lut2); }
+  static __device__ __forceinline__ uint32_t* dsum(uint32_t* smem) { return at<uint32_t>(smem, o_dsum); }
+  static __device__ __forceinline__ uint32_t* dacc(uint32_t* smem) { return at<uint32_t>(smem, o_dacc); }
+  static __device__ __forceinline__ uint2* breg(uint32_t* smem) { return at<uint2>(smem, o_breg); }
+};
+static_assert(Bin1Lds::bytes <= 160 * 1024, "one workgroup's LDS");
+static_assert(Bin1Lds::o_stage % 16 == 0 && Bin1Lds::o_heads % 16 == 0 && Bin1Lds::o_dw % 16 == 0 &&
+                  Bin1Lds::o_lut2 % 16 == 0 && Bin1Lds::o_breg % 16 == 0,
+              "stage and heads are accessed as uint4, dw, lut2 and breg as uint2");
+static_assert(2ull * CHW * (DSUM_PMAX - 1) < (1ull << 32),
+              "u32 direct sums: <= CHW (2^17 - 1) at a sub-chunk's start + as much from the sub-chunk");
+
+// The two packed words of level 1.  pk, a slot's place: rank in its bin [14:0] | bin [24:15].
+static_assert(CHW <= 32768 && BIN1_BINS <= 1024, "15-bit ranks, 10-bit bins");
+__device__ __forceinline__ uint32_t pk_make(uint32_t rank, uint32_t bin) { return rank | (bin << 15); }
+__device__ __forceinline__ uint32_t pk_rank(uint32_t pk) { return pk & 0x7FFFu; }
+__device__ __forceinline__ uint32_t pk_bin(uint32_t pk) { return (pk >> 15) & 1023u; }
+// offr, a bin's run: stage offset [15:0] | run rank [31:16] (the block scan adds both at once:
+// a sub-chunk's counts sum to <= CHW < 2^16, no carry)
+static_assert(CHW < 65536, "16-bit stage offsets");
+__device__ __forceinline__ uint32_t offr_make(uint32_t off, uint32_t run) { return off | (run << 16); }
+__device__ __forceinline__ uint32_t offr_off(uint32_t w) { return w & 0xFFFFu; }
+__device__ __forceinline__ uint32_t offr_run(uint32_t w) { return w >> 16; }
+
+// A bin's run of one sub-chunk, held by the bin's thread from the reservation to the run deltas.
+struct Bin1Run {
+  uint32_t n, old;     // records of the bin in this sub-chunk; the bin's cursor before them
+  uint32_t base, cap;  // the bin's region
+};
+
+// index of slot q of 16-B group kk of a sub-chunk at c0: 4 (kk NT1 + thread) + q, as loaded
+__device__ __forceinline__ uint32_t b1_slot(uint32_t c0, int kk, int q) {
+  return c0 + 4u * ((uint32_t)kk * NT1 + threadIdx.x) + (uint32_t)q;
+}
+
+// The phases of a sub-chunk (k_rbin1w below has the barriers between them).  Those of the
+// ranking loop take and return values, not references to the kernel's arrays, and the half
+// they load or rank is a plain argument.  A function is optimised by itself before it is
+// inlined, so how a phase is cut decides the kernel's code: with sv / fv / pk passed as array
+// references C3 was 1.5 % slower, with the half of b1_issue_half a template parameter (two
+// VGPRs fewer) 1.7 % slower, this form equal to the one-body kernel
+// (profiles/r08_level1_refactor.txt).  Measure level 1 after any change to a signature here.
+// A half's loads in flight (B1_HG 16-B groups of ids and of value bits), and a half's samples.
+struct Bin1Regs {
+  uint4 s[B1_HG], v[B1_HG];
+};
+struct Bin1Half {
+  uint32_t s[B1_PH];
+  float f[B1_PH];
+};
+
+// Issues the loads of half `h` of the full sub-chunk at c0.
+__device__ __forceinline__ Bin1Regs b1_issue_half(const uint32_t* series, const float* values, uint32_t c0, int h) {
+  Bin1Regs r;
+#pragma unroll
+  for (int k = 0; k < B1_HG; ++k) {
+    const uint32_t base = b1_slot(c0, h * B1_HG + k, 0);
+    r.s[k] = ld_stream(series + base);
+    r.v[k] = ld_stream(reinterpret_cast<const uint32_t*>(values) + base);
+  }
+  return r;
+}
+
+// A half's samples from the registers b1_issue_half filled (a full sub-chunk) ...
+__device__ __forceinline__ Bin1Half b1_unpack_half(Bin1Regs r) {
+  Bin1Half x;
+#pragma unroll
+  for (int k = 0; k < B1_HG; ++k) {
+    const uint4 s4 = r.s[k], u4 = r.v[k];
+    const float4 f4 = make_float4(__uint_as_float(u4.x), __uint_as_float(u4.y), __uint_as_float(u4.z),
+                                  __uint_as_float(u4.w));
+    x.s[4 * k] = s4.x; x.s[4 * k + 1] = s4.y; x.s[4 * k + 2] = s4.z; x.s[4 * k + 3] = s4.w;
+    x.f[4 * k] = f4.x; x.f[4 * k + 1] = f4.y; x.f[4 * k + 2] = f4.z; x.f[4 * k + 3] = f4.w;
+  }
+  return x;
+}
+// ... or slot by slot with bounds (the slab's ragged end, an unaligned batch): half h of the
+// sub-chunk at c0, a slot at or past hi an invalid id; and whether a slot below hi holds one.
+__device__ __forceinline__ Bin1Half b1_load_ragged(const uint32_t* series, const float* values, uint32_t c0,
+                                                   uint32_t hi, int h) {
+  Bin1Half x;
+#pragma unroll
+  for (int k = 0; k < B1_PH; ++k) {
+    const uint32_t i = b1_slot(c0, h * B1_HG + (k >> 2), k & 3);
+    const bool in = i < hi;
+    x.s[k] = in ? series[i] : 0xFFFFFFFFu;
+    x.f[k] = in ? values[i] : 0.0f;
+  }
+  return x;
+}
+__device__ __forceinline__ bool b1_ragged_invalid(Bin1Half x, uint32_t c0, uint32_t hi, int h, uint32_t S) {
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < B1_PH; ++k) bad |= b1_slot(c0, h * B1_HG + (k >> 2), k & 3) < hi && x.s[k] >= S;
+  return bad;
+}
+// Whether a slot of group g holds an invalid id (a full sub-chunk: every slot is a sample).
+__device__ __forceinline__ bool b1_group_invalid(Bin1Half x, int g, uint32_t S) {
+  bool bad = false;
+#pragma unroll
+  for (int q = 0; q < B1_GS; ++q) bad |= x.s[g + q] >= S;
+  return bad;
+}
+
+// Ranks the B1_GS slots g .. of half h: payload, record, bin, the rank atomic, the direct
+// series' sum add, and the records to the stage in slot order.  Returns the slots' pk words.
+static_assert(B1_GS == 4, "a group's pk words are returned as a uint4");
+__device__ __forceinline__ uint4 b1_rank_group(uint32_t* smem, int h, int g, Bin1Half x, const uint32_t* series,
+                                               const float* values, uint32_t c0, uint32_t S, uint32_t FS, uint32_t TB,
+                                               Tables tb, int64_t* sumfix, int pass) {
+  uint32_t* const stage = Bin1Lds::stage(smem);
+  uint32_t* const cnt = Bin1Lds::cnt(smem);
+  uint2* const dw = Bin1Lds::dw(smem);
+  uint2* const lut2 = Bin1Lds::lut2(smem);
+  uint32_t* const dsum = Bin1Lds::dsum(smem);
+  constexpr int GS = B1_GS;
+  uint32_t pl[GS], pk[GS];
+  uint32_t escm = 0;
+#pragma unroll
+  for (int q = 0; q < GS; ++q) {
+    // fast: +0 <= f < 2^17, one integer compare of the bit pattern (-0, NaN and (-1, 0) take
+    // the exact slow path, which also truncates them to 0); 2^17 and not V_ESC, so that the
+    // slow path sees the few payloads the u32 sums must not take
+    const float f = x.f[g + q];
+    const bool fast = __float_as_uint(f) < 0x48000000u;  // bits of 2^17f
+    pl[q] = fast ? (uint32_t)f : 0u;
+    escm |= (!fast && x.s[g + q] < S) ? (1u << q) : 0u;
+  }
+  if (__ballot(escm != 0u)) {
+    // one copy of the full search in the loop's code: slot q's sample is re-read
+    // from the batch (an L2 hit; the 4 slots of a group are consecutive samples).
+    // Picking it from the registers by a dynamic q made the compiler keep sv / fv
+    // in scratch: 24 scratch stores per thread per sub-chunk, each behind a wait
+    // for its load, on every sub-chunk (round 5).
+#pragma unroll 1
+    for (int q = 0; q < GS; ++q) {
+      if ((escm >> q) & 1u) {
+        const uint32_t i = b1_slot(c0, h * B1_HG + (g + q) / 4, q & 3);
+        const uint32_t si = series[i];
+        const uint32_t r = payload1_slow(si, values[i], tb, pass == 0 ? sumfix : nullptr);
+        if (pass == 0 && r - DSUM_PMAX < V_ESC - DSUM_PMAX) {
+          // not escaped, but too large for a u32 sum: a direct series' value goes to sumfix here
+          const uint2 d = dw[(si >> (TILE_SHIFT + 5)) & 1023u];
+          if ((d.x >> ((si >> TILE_SHIFT) & 31u)) & 1u)
+            atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[si]), (unsigned long long)r);
+        }
+#pragma unroll
+        for (int u = 0; u < GS; ++u) pl[u] = q == u ? r : pl[u];
+      }
+    }
+  }
+  uint2 dv[GS], lv[GS];
+#pragma unroll
+  for (int q = 0; q < GS; ++q) dv[q] = dw[(x.s[g + q] >> (TILE_SHIFT + 5)) & 1023u];  // (any word when s >= S)
+#pragma unroll
+  // the bucket LUT, read by every slot: issued with the dw reads instead of behind them
+  // (only a direct slot uses it; reading it under the direct bit waited for dw first:
+  // bin1 3.31 -> 3.25 ms on C3, C2 unchanged, round 5)
+  for (int q = 0; q < GS; ++q) lv[q] = lut2[lut2_index(pl[q])];
+  uint32_t rc4[GS];
+#pragma unroll
+  for (int q = 0; q < GS; ++q) {
+    const uint32_t s = x.s[g + q];
+    const uint32_t tw = __builtin_amdgcn_ubfe(s, TILE_SHIFT, 5);
+    const bool direct = s < S && __builtin_amdgcn_ubfe(dv[q].x, tw, 1) != 0u;
+    const uint32_t di = dv[q].y + (uint32_t)__popc(__builtin_amdgcn_ubfe(dv[q].x, 0, tw));
+    const uint32_t p = pl[q];
+    uint32_t o;
+    const uint32_t bk = lut2_decode(p, lv[q], o);
+    const bool esc = p >= V_ESC;
+    const uint32_t bucket = sel_u32(esc, p - V_ESC, bk);
+    rc4[q] = sel_u32(direct, ((s & (TILE - 1)) << 11) | bucket, ((s & (ST_TILES * TILE - 1)) << 21) | p);
+    const uint32_t dbin = FS + 2u * di + ((s >> 4) & 1u);
+    const uint32_t bn = sel_u32(s < S, sel_u32(direct, dbin, s >> ST_SHIFT), TB);
+    pk[q] = pk_make(atomicAdd(cnt + bn, 1u), bn);
+    // the direct series' value sum (no wrap to check -- see above -- so nothing reads the
+    // return); 0 < p < DSUM_PMAX (so not escaped) in one compare
+    if (direct && pass == 0 && p - 1u < DSUM_PMAX - 1u) atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], p);
+  }
+#pragma unroll
+  for (int j = 0; j < GS / 4; ++j)
+    *reinterpret_cast<uint4*>(stage + b1_slot(0u, h * B1_HG + g / 4 + j, 0)) =
+        make_uint4(rc4[4 * j], rc4[4 * j + 1], rc4[4 * j + 2], rc4[4 * j + 3]);
+  asm volatile("" ::: "memory");  // keep the groups apart (bounded register pressure)
+  return make_uint4(pk[0], pk[1], pk[2], pk[3]);
+}
+
+// Run reservation of bin tq (the trash bin TB gets none): one returning global atomic on
+// the bin's cursor if the sub-chunk has records of it.
+__device__ __forceinline__ Bin1Run b1_reserve_run(uint32_t* smem, uint32_t tq, uint32_t TB, uint32_t* bcnt) {
+  uint32_t* const cnt = Bin1Lds::cnt(smem);
+  uint2* const breg = Bin1Lds::breg(smem);
+  Bin1Run r;
+  r.n = tq <= TB ? cnt[tq] : 0u;
+  r.old = 0;
+  const uint2 reg = breg[tq];
+  r.base = reg.x;
+  r.cap = reg.y;
+  if (tq < TB && r.n) r.old = atomicAdd(&bcnt[tq], r.n);
+  return r;
+}
+
+// The u32 sums' guard (no add is in flight here): direct half-bin tq's records since its
+// flush; a bin over the bound is flushed by 16 lanes of its owner's wave, one sum each.
+__device__ __forceinline__ void b1_guard_flush(uint32_t* smem, uint32_t tq, uint32_t rn, uint32_t FS, uint32_t TB,
+                                               const uint32_t* meta, uint32_t dlist, uint32_t S, int64_t* sumfix) {
+  uint32_t* const dsum = Bin1Lds::dsum(smem);
+  uint32_t* const dacc = Bin1Lds::dacc(smem);
+  bool fl = false;
+  if (tq >= FS && tq < TB && rn) {
+    const uint32_t A = dacc[tq] + rn;
+    fl = A > (uint32_t)CHW;
+    dacc[tq] = fl ? 0u : A;
+  }
+  for (uint64_t fm = __ballot(fl); fm; fm &= fm - 1) {  // (wave-uniform, rarely non-zero)
+    const uint32_t fb = (tq & ~63u) + (uint32_t)__builtin_ctzll(fm) - FS;  // direct half-bin
+    if ((tq & 63u) < TILE / 2) {
+      const uint32_t h = fb * (TILE / 2) + (tq & 63u);  // = di * TILE + series in tile
+      const uint32_t v = dsum[h];
+      dsum[h] = 0;
+      const uint32_t sr = meta[dlist + h / TILE] * TILE + (h & (TILE - 1));
+      if (v && sr < S) atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[sr]), (unsigned long long)v);
+    }
+  }
+}
+
+// Block scan of {count, non-empty}, one bin per thread, in two steps around B1b: the wave's
+// inclusive scan and its total to wsum; then the bin's stage offset and run rank, and its
+// run head's bit.
+__device__ __forceinline__ uint32_t b1_scan_waves(uint32_t pv, uint32_t tq, uint32_t* wsum) {
+  const uint32_t wi = wave_incl_scan32(pv);
+  if ((tq & 63u) == 63u) wsum[tq >> 6] = wi;
+  return wi;
+}
+__device__ __forceinline__ void b1_scan_heads(uint32_t* smem, const uint32_t* wsum, int wv, uint32_t pv, uint32_t wi,
+                                              uint32_t rn) {
+  uint32_t* const offr = Bin1Lds::offr(smem);
+  uint32_t* const heads = Bin1Lds::heads(smem);
+  uint32_t pre = 0;
+  for (int q = 0; q < wv; ++q) pre += wsum[q];
+  const uint32_t ex = pre + wi - pv;
+  offr[threadIdx.x] = ex;
+  if (rn) atomicOr(&heads[offr_off(ex) >> 5], 1u << (ex & 31u));
+}
+
+// This thread's records, in slot order (read before any is scattered).
+__device__ __forceinline__ void b1_read_slots(uint32_t* smem, uint32_t (&rec)[B1_PT]) {
+  uint32_t* const stage = Bin1Lds::stage(smem);
+#pragma unroll
+  for (int kk = 0; kk < B1_PT / 4; ++kk) {
+    const uint4 v = *reinterpret_cast<const uint4*>(stage + b1_slot(0u, kk, 0));
+    rec[4 * kk] = v.x; rec[4 * kk + 1] = v.y; rec[4 * kk + 2] = v.z; rec[4 * kk + 3] = v.w;
+  }
+}
+
+// A record to its bin's run in the stage, at its rank.
+__device__ __forceinline__ void b1_scatter(uint32_t* smem, uint32_t pk, uint32_t rec) {
+  uint32_t* const stage = Bin1Lds::stage(smem);
+  uint32_t* const offr = Bin1Lds::offr(smem);
+  stage[offr_off(offr[pk_bin(pk)]) + pk_rank(pk)] = rec;
+}
+
+// Runs before group g = run heads in the groups before it (one wave: a scan of popcounts).
+__device__ __forceinline__ void b1_group_prefixes(uint32_t* smem, int lane) {
+  uint32_t* const heads = Bin1Lds::heads(smem);
+  uint16_t* const gpre = Bin1Lds::gpre(smem);
+  constexpr int GPL = CHW / 64 / 64;  // groups per lane
+  static_assert(GPL % 2 == 0, "two groups per 16-B read");
+  uint32_t pc[GPL], t = 0;
+#pragma unroll
+  for (int k = 0; k < GPL; k += 2) {
+    const uint4 w = *reinterpret_cast<const uint4*>(heads + 2u * (GPL * (uint32_t)lane + (uint32_t)k));
+    pc[k] = (uint32_t)(__popc(w.x) + __popc(w.y));
+    pc[k + 1] = (uint32_t)(__popc(w.z) + __popc(w.w));
+    t += pc[k] + pc[k + 1];
+  }
+  uint32_t ex = wave_incl_scan32(t) - t;
+#pragma unroll
+  for (int k = 0; k < GPL; ++k) {
+    gpre[GPL * (uint32_t)lane + (uint32_t)k] = (uint16_t)ex;
+    ex += pc[k];
+  }
+}
+
+// The run's destination delta, by run rank; a run that does not fit its region is dropped
+// and flagged (k_rfix1 has the batch redone with exact regions).
+__device__ __forceinline__ void b1_run_delta(uint32_t* smem, const Bin1Run& r, uint32_t TB, uint32_t* hdr) {
+  uint32_t* const offr = Bin1Lds::offr(smem);
+  uint32_t* const rdelta = Bin1Lds::rdelta(smem);
+  const uint32_t b = threadIdx.x;
+  if (r.n) {
+    uint32_t d = NODEST;
+    if (b < TB) {
+      if (r.old + r.n <= r.cap) d = r.base + r.old - offr_off(offr[b]);
+      else hdr[H_OV1] = 1u;
+    }
+    rdelta[offr_run(offr[b])] = d;
+  }
+}
+
+// All CHW stage entries, in sorted order (each wave a contiguous B1_PT x 64 range), to their
+// runs' regions: runs below nst are u32 records, the later runs u16.
+__device__ __forceinline__ void b1_write_out(uint32_t* smem, int wv, int lane, uint32_t nst, uint32_t* rec32,
+                                             uint16_t* rec16) {
+  uint32_t* const stage = Bin1Lds::stage(smem);
+  uint32_t* const rdelta = Bin1Lds::rdelta(smem);
+  uint32_t* const heads = Bin1Lds::heads(smem);
+  uint16_t* const gpre = Bin1Lds::gpre(smem);
+#pragma unroll 4
+  for (int k = 0; k < B1_PT; ++k) {
+    const uint32_t i = (uint32_t)wv * (B1_PT * 64) + (uint32_t)k * 64 + (uint32_t)lane;
+    const uint32_t g = i >> 6;  // (wave-uniform)
+    const unsigned long long hw = *reinterpret_cast<const unsigned long long*>(heads + 2 * g);
+    // run heads at or before this lane: those below it (mbcnt) + its own bit
+    const uint32_t run = (uint32_t)gpre[g] + mask_below(hw) + (uint32_t)((hw >> lane) & 1ull) - 1u;
+    const uint32_t d = rdelta[run];
+    if (d != NODEST) {
+      if (run < nst)
+        rec32[i + d] = stage[i];
+      else
+        rec16[i + d] = (uint16_t)stage[i];
+    }
+  }
+}
+
+// The slab's direct value sums (every wave's adds are in: the last barrier) into sumfix.
+__device__ __forceinline__ void b1_flush_sums(uint32_t* smem, uint32_t ND, const uint32_t* dlist, uint32_t S,
+                                              int64_t* sumfix) {
+  uint32_t* const dsum = Bin1Lds::dsum(smem);
+  for (uint32_t i = threadIdx.x; i < ND * TILE; i += NT1) {
+    const unsigned long long v = dsum[i];
+    const uint32_t s = dlist[i / TILE] * TILE + (i & (TILE - 1));
+    if (v && s < S) atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[s]), (unsigned long long)v);
+  }
+}
+
+__global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ series, const float* __restrict__ values,
+                                                size_t n, size_t per, uint32_t S, uint32_t F, Tables tb,
+                                                uint32_t* __restrict__ meta, uint32_t* __restrict__ rec32,
+                                                uint16_t* __restrict__ rec16, int64_t* __restrict__ sumfix,
+                                                uint32_t* __restrict__ err, int vec, int pass) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  uint32_t* stage = smem;                                        // [CH] records, sorted by bin
-  uint32_t* cnt = stage + CH;                                    // [BIN1_BINS]
-  uint32_t* offr = cnt + BIN1_BINS;                              // [BIN1_BINS] stage offset | run rank << 16
-  uint32_t* rdelta = offr + BIN1_BINS;                           // [BIN1_BINS] by run rank
-  uint32_t* heads = rdelta + BIN1_BINS;                          // [CH / 32] run heads
-  uint16_t* gpre = reinterpret_cast<uint16_t*>(heads + CH / 32);  // [CH / 64] runs before each 64-entry group
-  uint2* dw = reinterpret_cast<uint2*>(gpre + CH / 64);          // [1024] {direct bits, direct tiles before}
-  uint2* lut2 = dw + 1024;                                       // [LUT2_N]
-  __shared__ uint32_t wsum[NT / 64];
-  DS* dsum = reinterpret_cast<DS*>(lut2 + LUT2_N);               // [DSUM_N] direct series value sums
-  uint32_t* dacc = reinterpret_cast<uint32_t*>(dsum + DSUM_N);   // [BIN1_BINS] (u32 sums) records since a bin's flush
-  uint2* breg = reinterpret_cast<uint2*>(dacc + BIN1_BINS);      // [BIN1_BINS] (u32 sums) region {base, capacity}
+  __shared__ uint32_t wsum[NT1 / 64];
+  uint32_t* const cnt = Bin1Lds::cnt(smem);
+  uint32_t* const offr = Bin1Lds::offr(smem);
+  uint32_t* const heads = Bin1Lds::heads(smem);
+  uint2* const dw = Bin1Lds::dw(smem);
+  uint2* const lut2 = Bin1Lds::lut2(smem);
+  uint32_t* const dsum = Bin1Lds::dsum(smem);
+  uint32_t* const dacc = Bin1Lds::dacc(smem);
+  uint2* const breg = Bin1Lds::breg(smem);
   const MetaLayout L = meta_layout(F);
   uint32_t* hdr = meta + L.hdr();
   if (pass == 1 && __builtin_amdgcn_readfirstlane(hdr[H_REDO1]) == 0u) return;
   uint32_t* bcnt = meta + L.bcnt();
   const uint32_t* bbase = meta + L.bbase();
   const uint32_t* bcap = meta + L.bcap();
+  const uint32_t* dlist = meta + L.dlist();
   const uint32_t FS = (F + ST_TILES - 1) / ST_TILES;
   const uint32_t NW = (F + 31) / 32;
   const uint32_t ND = hdr[H_ND];
   const uint32_t TB = FS + 2 * ND;
   const int lane = lane_id();
   const int wv = threadIdx.x >> 6;
-  for (uint32_t w = threadIdx.x; w < NW; w += NT) dw[w] = make_uint2(meta[L.dbits() + w], meta[L.dpre() + w]);
-  for (uint32_t b = threadIdx.x; b < BIN1_BINS; b += NT) {
-    cnt[b] = 0;
-    if (S32) dacc[b] = 0;
-  }
-  for (uint32_t i = threadIdx.x; i < LUT2_N; i += NT) lut2[i] = tb.lut2[i];
-  for (uint32_t i = threadIdx.x; i < ND * TILE; i += NT) dsum[i] = 0;
+  for (uint32_t w = threadIdx.x; w < NW; w += NT1) dw[w] = make_uint2(meta[L.dbits() + w], meta[L.dpre() + w]);
+  cnt[threadIdx.x] = 0;
+  dacc[threadIdx.x] = 0;
+  for (uint32_t i = threadIdx.x; i < LUT2_N; i += NT1) lut2[i] = tb.lut2[i];
+  for (uint32_t i = threadIdx.x; i < ND * TILE; i += NT1) dsum[i] = 0;
   __syncthreads();
   // (a batch piece holds < 2^30 samples: 32-bit sample indices)
   const uint32_t lo = (uint32_t)((size_t)blockIdx.x * per);
   const uint32_t hi = (uint32_t)min((size_t)lo + per, n);
   bool bad = false;
-  // this thread's bins' regions (fixed for the launch): loaded once, not per sub-chunk
-  constexpr int RB0 = (BIN1_BINS + NT - 1) / NT;
-  uint32_t my_base[RB0], my_cap[RB0];
-#pragma unroll
-  for (int j = 0; j < RB0; ++j) {
-    const uint32_t b = threadIdx.x + (uint32_t)j * NT;
-    my_base[j] = b < TB ? bbase[b] : 0u;
-    my_cap[j] = b < TB ? bcap[b] : 0u;
-    if (S32) breg[b] = make_uint2(my_base[j], my_cap[j]);  // (read back by this thread alone)
+  {  // this thread's bin's region (fixed for the launch): loaded once, read back by this thread alone
+    const uint32_t b = threadIdx.x;
+    breg[b] = b < TB ? make_uint2(bbase[b], bcap[b]) : make_uint2(0u, 0u);
   }
   PH_INIT
-  // the next sub-chunk's first half loaded during this one's scatter / write-out
-  constexpr int PFG = PH / 4;  // prefetched 16-B groups per array
-  uint4 pfs[PFG], pfv[PFG];
-  auto prefetch = [&](uint32_t c) {
-#pragma unroll
-    for (int k = 0; k < PFG; ++k) {
-      const uint32_t base = c + 4u * ((uint32_t)k * NT + threadIdx.x);
-      pfs[k] = ld_stream(series + base);
-      pfv[k] = ld_stream(reinterpret_cast<const uint32_t*>(values) + base);
-    }
-  };
-  if (vec && lo + (uint32_t)CH <= hi) prefetch(lo);
-  for (uint32_t c0 = lo; c0 < hi; c0 += CH) {
-    for (uint32_t wd = threadIdx.x; wd < CH / 32; wd += NT) heads[wd] = 0u;
+  // the next sub-chunk's first half, loaded during this one's scatter / write-out
+  Bin1Regs pf;
+  if (vec && lo + (uint32_t)CHW <= hi) pf = b1_issue_half(series, values, lo, 0);
+  for (uint32_t c0 = lo; c0 < hi; c0 += CHW) {
+    for (uint32_t wd = threadIdx.x; wd < CHW / 32; wd += NT1) heads[wd] = 0u;
     // records are staged in slot order first (the stage is free until the scatter), so
     // only their ranks and bins stay in registers while the sub-chunk is ranked
-    uint32_t pk[PT];  // [14:0] rank | [24:15] bin
-    const bool full = vec && c0 + (uint32_t)CH <= hi;
-    const uint32_t cl = c0;
-    // the second half, issued once the first half's first group is ranked (in flight through
-    // the rest of its ranking): bin1 3.25-3.30 -> 3.18 ms on C3 (issued before the first group,
-    // or at the second half's start as in round 4, 3.36 / 3.25; profiles/r05w_second_half_ab.txt)
-    uint4 hs[PH / 4], hv[PH / 4];
-    auto load_second = [&]() {
-      if (full) {
-#pragma unroll
-        for (int k = 0; k < PH / 4; ++k) {
-          const uint32_t base = cl + 4u * ((uint32_t)(PH / 4 + k) * NT + threadIdx.x);
-          hs[k] = ld_stream(series + base);
-          hv[k] = ld_stream(reinterpret_cast<const uint32_t*>(values) + base);
-        }
-      }
-    };
+    uint32_t pk[B1_PT];
+    const bool full = vec && c0 + (uint32_t)CHW <= hi;
+    Bin1Regs sh;  // the second half's loads
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (h == 1) { PH_MARK(1) }
-      uint32_t sv[PH];
-      float fv[PH];
+      Bin1Half hf;
       if (full) {
-#pragma unroll
-        for (int k = 0; k < PH / 4; ++k) {
-          uint4 s4, u4;
-          if (h == 0) {
-            s4 = pfs[h * (PH / 4) + k];
-            u4 = pfv[h * (PH / 4) + k];
-          } else {
-            s4 = hs[k];
-            u4 = hv[k];
-          }
-          const float4 f4 = make_float4(__uint_as_float(u4.x), __uint_as_float(u4.y), __uint_as_float(u4.z),
-                                        __uint_as_float(u4.w));
-          sv[4 * k] = s4.x; sv[4 * k + 1] = s4.y; sv[4 * k + 2] = s4.z; sv[4 * k + 3] = s4.w;
-          fv[4 * k] = f4.x; fv[4 * k + 1] = f4.y; fv[4 * k + 2] = f4.z; fv[4 * k + 3] = f4.w;
-        }
+        hf = b1_unpack_half(h == 0 ? pf : sh);
       } else {
-#pragma unroll
-        for (int k = 0; k < PH; ++k) {
-          const uint32_t i = c0 + 4u * ((uint32_t)(h * (PH / 4) + (k >> 2)) * NT + threadIdx.x) + (uint32_t)(k & 3);
-          const bool in = i < hi;
-          sv[k] = in ? series[i] : 0xFFFFFFFFu;
-          fv[k] = in ? values[i] : 0.0f;
-          bad |= in && sv[k] >= S;
-        }
+        hf = b1_load_ragged(series, values, c0, hi, h);
+        bad |= b1_ragged_invalid(hf, c0, hi, h, S);
       }
       if (full) {  // (phase stamps: the half's loads -- and, on gfx9, every older store -- done)
         PH_VWAIT
         if (h == 0) { PH_MARK(0) } else { PH_MARK(2) }
       }
 #pragma unroll
-      for (int g = 0; g < PH; g += GS) {
-        if (h == 0 && g == GS) load_second();
-        uint32_t pl[GS];
-        uint32_t escm = 0;
-#pragma unroll
-        for (int q = 0; q < GS; ++q) {
-          // fast: +0 <= f < V_ESC, one integer compare of the bit pattern (-0, NaN and
-          // (-1, 0) take the exact slow path, which also truncates them to 0); with u32 sums
-          // f < DSUM_PMAX, so that the slow path sees the few payloads the sums must not take
-          const float f = fv[g + q];
-          const bool fast = __float_as_uint(f) < (S32 ? 0x48000000u : 0x49FFC000u);  // bits of 2^17 / (float)V_ESC
-          pl[q] = fast ? (uint32_t)f : 0u;
-          escm |= (!fast && sv[g + q] < S) ? (1u << q) : 0u;
-          if (full) bad |= sv[g + q] >= S;
-        }
-        if (__ballot(escm != 0u)) {
-          // one copy of the full search in the loop's code: slot q's sample is re-read
-          // from the batch (an L2 hit; the 4 slots of a group are consecutive samples).
-          // Picking it from the registers by a dynamic q made the compiler keep sv / fv
-          // in scratch: 24 scratch stores per thread per sub-chunk, each behind a wait
-          // for its load, on every sub-chunk (round 5).
-#pragma unroll 1
-          for (int q = 0; q < GS; ++q) {
-            if ((escm >> q) & 1u) {
-              const uint32_t i = cl + 4u * ((uint32_t)(h * (PH / 4) + (g + q) / 4) * NT + threadIdx.x) + (uint32_t)(q & 3);
-              const uint32_t si = series[i];
-              const uint32_t r = payload1_slow(si, values[i], tb, pass == 0 ? sumfix : nullptr);
-              if (S32 && pass == 0 && r - DSUM_PMAX < V_ESC - DSUM_PMAX) {
-                // not escaped, but too large for a u32 sum: a direct series' value goes to sumfix here
-                const uint2 d = dw[(si >> (TILE_SHIFT + 5)) & 1023u];
-                if ((d.x >> ((si >> TILE_SHIFT) & 31u)) & 1u)
-                  atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[si]), (unsigned long long)r);
-              }
-#pragma unroll
-              for (int u = 0; u < GS; ++u) pl[u] = q == u ? r : pl[u];
-            }
-          }
-        }
-        uint2 dv[GS], lv[GS];
-#pragma unroll
-        for (int q = 0; q < GS; ++q) dv[q] = dw[(sv[g + q] >> (TILE_SHIFT + 5)) & 1023u];  // (any word when s >= S)
-#pragma unroll
-        // the bucket LUT, read by every slot: issued with the dw reads instead of behind them
-        // (only a direct slot uses it; reading it under the direct bit waited for dw first:
-        // bin1 3.31 -> 3.25 ms on C3, C2 unchanged, round 5)
-        for (int q = 0; q < GS; ++q) lv[q] = lut2[lut2_index(pl[q])];
-        uint32_t rc4[GS];
-#pragma unroll
-        for (int q = 0; q < GS; ++q) {
-          const uint32_t s = sv[g + q];
-          const uint32_t tw = __builtin_amdgcn_ubfe(s, TILE_SHIFT, 5);
-          const bool direct = s < S && __builtin_amdgcn_ubfe(dv[q].x, tw, 1) != 0u;
-          const uint32_t di = dv[q].y + (uint32_t)__popc(__builtin_amdgcn_ubfe(dv[q].x, 0, tw));
-          const uint32_t p = pl[q];
-          uint32_t o;
-          const uint32_t bk = lut2_decode(p, lv[q], o);
-          const bool esc = p >= V_ESC;
-          const uint32_t bucket = sel_u32(esc, p - V_ESC, bk);
-          rc4[q] = sel_u32(direct, ((s & (TILE - 1)) << 11) | bucket, ((s & (ST_TILES * TILE - 1)) << 21) | p);
-          const uint32_t dbin = FS + 2u * di + ((s >> 4) & 1u);
-          const uint32_t bn = sel_u32(s < S, sel_u32(direct, dbin, s >> ST_SHIFT), TB);
-          pk[h * PH + g + q] = atomicAdd(cnt + bn, 1u) | (bn << 15);
-          // the direct series' value sum (no wrap to check -- see above -- so nothing reads the return)
-          if (S32) {  // 0 < p < DSUM_PMAX (so not escaped) in one compare
-            if (direct && pass == 0 && p - 1u < DSUM_PMAX - 1u) atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], (DS)p);
-          } else if (direct && !esc && pass == 0 && p) {
-            atomicAdd(&dsum[di * TILE + (s & (TILE - 1))], (DS)p);
-          }
-        }
-        // slots 4 (kk NT + thread) + q of the 16-B group kk, as loaded
-#pragma unroll
-        for (int j = 0; j < GS / 4; ++j)
-          *reinterpret_cast<uint4*>(stage + 4u * ((uint32_t)(h * (PH / 4) + g / 4 + j) * NT + threadIdx.x)) =
-              make_uint4(rc4[4 * j], rc4[4 * j + 1], rc4[4 * j + 2], rc4[4 * j + 3]);
-        asm volatile("" ::: "memory");  // keep the groups apart (bounded register pressure)
+      for (int g = 0; g < B1_PH; g += B1_GS) {
+        // the second half, issued once the first half's first group is ranked (in flight through
+        // the rest of its ranking): bin1 3.25-3.30 -> 3.18 ms on C3 (issued before the first group,
+        // or at the second half's start as in round 4, 3.36 / 3.25; profiles/r05w_second_half_ab.txt)
+        if (h == 0 && g == B1_GS && full) sh = b1_issue_half(series, values, c0, 1);
+        if (full) bad |= b1_group_invalid(hf, g, S);
+        const uint4 p4 = b1_rank_group(smem, h, g, hf, series, values, c0, S, FS, TB, tb, sumfix, pass);
+        pk[h * B1_PH + g] = p4.x; pk[h * B1_PH + g + 1] = p4.y; pk[h * B1_PH + g + 2] = p4.z; pk[h * B1_PH + g + 3] = p4.w;
       }
     }
     __syncthreads();  // B1: counts complete
     PH_MARK(3)
-    // run reservations: thread t -> bins t, t + NT, ... (the trash bin TB gets none)
-    constexpr int RB = (BIN1_BINS + NT - 1) / NT;
-    uint32_t rn[RB], rold[RB], rbase[RB], rcapv[RB];
-    // (u32 sums: this phase's per-thread addresses are computed here, once per sub-chunk, not
-    // hoisted out of the sub-chunk loop into registers the ranking needs)
+    // (this phase's per-thread addresses are computed here, once per sub-chunk, not hoisted
+    // out of the sub-chunk loop into registers the ranking needs)
     uint32_t tq = threadIdx.x;
-    if (S32) asm volatile("" : "+v"(tq));
-#pragma unroll
-    for (int j = 0; j < RB; ++j) {
-      const uint32_t rb_bin = tq + (uint32_t)j * NT;
-      rn[j] = rb_bin <= TB ? cnt[rb_bin] : 0u;  // records of the bin in this sub-chunk
-      rold[j] = 0;
-      if (S32) {
-        const uint2 r = breg[rb_bin];
-        rbase[j] = r.x;
-        rcapv[j] = r.y;
-      } else {
-        rbase[j] = my_base[j];
-        rcapv[j] = my_cap[j];
-      }
-      if (rb_bin < TB && rn[j]) rold[j] = atomicAdd(&bcnt[rb_bin], rn[j]);
-    }
-    if (S32 && pass == 0) {
-      // the u32 sums' guard (no add is in flight here): this direct half-bin's records since its
-      // flush; a bin over the bound is flushed by 16 lanes of its owner's wave, one sum each
-      bool fl = false;
-      if (tq >= FS && tq < TB && rn[0]) {
-        const uint32_t A = dacc[tq] + rn[0];
-        fl = A > (uint32_t)CH;
-        dacc[tq] = fl ? 0u : A;
-      }
-      for (uint64_t fm = __ballot(fl); fm; fm &= fm - 1) {  // (wave-uniform, rarely non-zero)
-        const uint32_t fb = (tq & ~63u) + (uint32_t)__builtin_ctzll(fm) - FS;  // direct half-bin
-        if ((tq & 63u) < TILE / 2) {
-          const uint32_t h = fb * (TILE / 2) + (tq & 63u);  // = di * TILE + series in tile
-          const uint32_t v = (uint32_t)dsum[h];
-          dsum[h] = 0;
-          const uint32_t sr = meta[L.dlist() + h / TILE] * TILE + (h & (TILE - 1));
-          if (v && sr < S) atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[sr]), (unsigned long long)v);
-        }
-      }
-    }
-    {  // stage offsets and run ranks: a block scan of {count, non-empty} (one bin per thread), run heads
-      static_assert(NT == BIN1_BINS && RB == 1, "one bin per thread");
-      const uint32_t pv = rn[0] | ((rn[0] ? 1u : 0u) << 16);  // (counts sum to <= CH < 2^16: no carry)
-      const uint32_t wi = wave_incl_scan32(pv);
-      if ((tq & 63u) == 63u) wsum[tq >> 6] = wi;
-      __syncthreads();  // B1b: wave totals
-      uint32_t pre = 0;
-      for (int q = 0; q < wv; ++q) pre += wsum[q];
-      const uint32_t ex = pre + wi - pv;
-      offr[threadIdx.x] = ex;  // offset | run rank << 16
-      if (rn[0]) atomicOr(&heads[(ex & 0xFFFFu) >> 5], 1u << (ex & 31u));
-    }
-    uint32_t rec[PT];  // this thread's records, in slot order (read before any is scattered)
-#pragma unroll
-    for (int kk = 0; kk < PT / 4; ++kk) {
-      const uint4 v = *reinterpret_cast<const uint4*>(stage + 4u * ((uint32_t)kk * NT + threadIdx.x));
-      rec[4 * kk] = v.x; rec[4 * kk + 1] = v.y; rec[4 * kk + 2] = v.z; rec[4 * kk + 3] = v.w;
-    }
+    asm volatile("" : "+v"(tq));
+    const Bin1Run run = b1_reserve_run(smem, tq, TB, bcnt);
+    if (pass == 0) b1_guard_flush(smem, tq, run.n, FS, TB, meta, L.dlist(), S, sumfix);
+    const uint32_t pv = offr_make(run.n, run.n ? 1u : 0u);
+    const uint32_t wi = b1_scan_waves(pv, tq, wsum);
+    __syncthreads();  // B1b: wave totals
+    b1_scan_heads(smem, wsum, wv, pv, wi, run.n);
+    uint32_t rec[B1_PT];
+    b1_read_slots(smem, rec);
     __syncthreads();  // B2: offsets, run ranks, heads; every slot-order record read
     PH_MARK(4)
     // (after B2: the run reservations' returns and the scan never wait behind these loads)
-    if (vec && c0 + 2u * (uint32_t)CH <= hi) prefetch(c0 + (uint32_t)CH);
+    if (vec && c0 + 2u * (uint32_t)CHW <= hi) pf = b1_issue_half(series, values, c0 + (uint32_t)CHW, 0);
 #pragma unroll
-    for (int k = 0; k < PT; ++k) {
-      const uint32_t bin = (pk[k] >> 15) & 1023u;
-      stage[(offr[bin] & 0xFFFFu) + (pk[k] & 0x7FFFu)] = rec[k];
-    }
-    if (wv == 0) {  // runs before group g = run heads in the groups before it (one wave: a scan of popcounts)
-      constexpr int GPL = CH / 64 / 64;  // groups per lane
-      static_assert(GPL % 2 == 0, "two groups per 16-B read");
-      uint32_t pc[GPL], t = 0;
-#pragma unroll
-      for (int k = 0; k < GPL; k += 2) {
-        const uint4 w = *reinterpret_cast<const uint4*>(heads + 2u * (GPL * (uint32_t)lane + (uint32_t)k));
-        pc[k] = (uint32_t)(__popc(w.x) + __popc(w.y));
-        pc[k + 1] = (uint32_t)(__popc(w.z) + __popc(w.w));
-        t += pc[k] + pc[k + 1];
-      }
-      uint32_t ex = wave_incl_scan32(t) - t;
-#pragma unroll
-      for (int k = 0; k < GPL; ++k) {
-        gpre[GPL * (uint32_t)lane + (uint32_t)k] = (uint16_t)ex;
-        ex += pc[k];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RB; ++j) {
-      const uint32_t rb_bin = threadIdx.x + (uint32_t)j * NT;
-      if (rn[j]) {
-        uint32_t d = NODEST;
-        if (rb_bin < TB) {
-          if (rold[j] + rn[j] <= rcapv[j]) d = rbase[j] + rold[j] - (offr[rb_bin] & 0xFFFFu);
-          else hdr[H_OV1] = 1u;  // this run is dropped; k_rfix1 has the batch redone with exact regions
-        }
-        rdelta[offr[rb_bin] >> 16] = d;
-      }
-    }
+    for (int k = 0; k < B1_PT; ++k) b1_scatter(smem, pk[k], rec[k]);
+    if (wv == 0) b1_group_prefixes(smem, lane);
+    b1_run_delta(smem, run, TB, hdr);
     __syncthreads();  // B3: stage, group prefixes, deltas (every count read: cleared below)
     PH_MARK(5)
-    const uint32_t nst = offr[FS] >> 16;  // runs of super-tile bins (u32 records); the later runs are u16
-#pragma unroll
-    for (int j = 0; j < RB; ++j)
-      if (threadIdx.x + (uint32_t)j * NT < BIN1_BINS) cnt[threadIdx.x + (uint32_t)j * NT] = 0;
-#pragma unroll 4
-    for (int k = 0; k < PT; ++k) {  // all CH entries, in sorted order (each wave a contiguous PT x 64 range)
-      const uint32_t i = (uint32_t)wv * (PT * 64) + (uint32_t)k * 64 + (uint32_t)lane;
-      const uint32_t g = i >> 6;  // (wave-uniform)
-      const unsigned long long hw = *reinterpret_cast<const unsigned long long*>(heads + 2 * g);
-      // run heads at or before this lane: those below it (mbcnt) + its own bit
-      const uint32_t run = (uint32_t)gpre[g] + mask_below(hw) + (uint32_t)((hw >> lane) & 1ull) - 1u;
-      const uint32_t d = rdelta[run];
-      if (d != NODEST) {
-        if (run < nst)
-          rec32[i + d] = stage[i];
-        else
-          rec16[i + d] = (uint16_t)stage[i];
-      }
-    }
+    const uint32_t nst = offr_run(offr[FS]);  // runs of super-tile bins
+    cnt[threadIdx.x] = 0;
+    b1_write_out(smem, wv, lane, nst, rec32, rec16);
     __syncthreads();  // B4
     PH_MARK(6)
   }
   PH_FLUSH
   if (pass == 0) {
-    // the slab's direct value sums (every wave's adds are in: the last barrier) into sumfix
-    const uint32_t* dl = meta + L.dlist();
-    for (uint32_t i = threadIdx.x; i < ND * TILE; i += NT) {
-      const unsigned long long v = dsum[i];
-      const uint32_t s = dl[i / TILE] * TILE + (i & (TILE - 1));
-      if (v && s < S) atomicAdd(reinterpret_cast<unsigned long long*>(&sumfix[s]), (unsigned long long)v);
-    }
+    b1_flush_sums(smem, ND, dlist, S, sumfix);
     if (bad) atomicAdd(err, 1u);  // monotonic: the host compares it with the count it already reported
   }
 }
@@ -1382,15 +1510,11 @@ hipError_t launch_fetch_host(const uint32_t* hs, const uint32_t* hv, uint32_t* d
 
 hipError_t set_ingest_attributes() {
   hipError_t e;
-  if ((e = hipFuncSetAttribute((const void*)k_rbin1w<NT1, CHW, unsigned long long>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)rbin1w_lds(8))))
-    return e;
   if ((e = hipFuncSetAttribute((const void*)k_rsample, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4)))
     return e;
   if ((e = hipFuncSetAttribute((const void*)k_rplan1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RPLAN1_LDS)))
     return e;
-  return hipFuncSetAttribute((const void*)k_rbin1w<NT1, CHW, uint32_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)rbin1w_lds(4));
+  return hipFuncSetAttribute((const void*)k_rbin1w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Bin1Lds::bytes);
 }
 
 hipError_t launch_ingest(const IngestArgs& a, int stage, hipStream_t st) {
@@ -1409,14 +1533,8 @@ hipError_t launch_ingest(const IngestArgs& a, int stage, hipStream_t st) {
       break;
     case 1:  // level 1, its fix-up, the redo pass (exits at once unless needed)
       for (int pass = 0; pass < 2; ++pass) {
-        if (a.dsum64)
-          hipLaunchKernelGGL((k_rbin1w<NT1, CHW, unsigned long long>), dim3(a.G), dim3(NT1), rbin1w_lds(8), st, a.series,
-                             a.values, a.n, a.per, a.S, a.F, a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err,
-                             a.vec ? 1 : 0, pass);
-        else
-          hipLaunchKernelGGL((k_rbin1w<NT1, CHW, uint32_t>), dim3(a.G), dim3(NT1), rbin1w_lds(4), st, a.series,
-                             a.values, a.n, a.per, a.S, a.F, a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err,
-                             a.vec ? 1 : 0, pass);
+        hipLaunchKernelGGL(k_rbin1w, dim3(a.G), dim3(NT1), Bin1Lds::bytes, st, a.series, a.values, a.n, a.per, a.S, a.F,
+                           a.tb, a.meta, a.rec32, a.rec16, a.sumfix, a.err, a.vec ? 1 : 0, pass);
         if (pass == 0) hipLaunchKernelGGL(k_rfix1, dim3(1), dim3(1024), 0, st, a.F, a.meta, a.err, a.err_host);
       }
       break;

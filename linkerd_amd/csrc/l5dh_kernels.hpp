@@ -182,7 +182,6 @@ struct IngestArgs {
   uint32_t thr_min, dmax;  // direct tiles: >= thr_min estimated records, at most dmax of them
   uint32_t pct;            // region capacity scale, percent (100: as predicted)
   bool vec;                // 16-B aligned inputs
-  bool dsum64;             // level 1's direct value sums in u64 LDS words (variant bit 3; default: guarded u32)
 };
 // Stages: 0 = sample + plans (level-1 bins and direct tiles, level-2 regions), 1 = level 1
 // (+ its fix-up: exact totals, level-2 items; + redo), 3 = level 2 (+ fix-up, redo).
