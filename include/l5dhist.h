@@ -253,6 +253,62 @@ int l5dh_le(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* cuts,
 int l5dh_le_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals /* nullable */, size_t n,
                   const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate);
 
+/* Java number texts, as the exporters print them (host only, no context): Long.toString,
+ * the unsigned 64-bit decimal (the `le` counts) and Double.toString as JDK 8 prints it
+ * (FloatingDecimal: not the shortest round-trip form of later JDKs; 2.82879384806159e17
+ * prints as 2.82879384806159008E17).  out receives *len characters, no terminator.
+ * l5dh_format_double handles +-0.0, NaN, +-Infinity and finite 2^-64 <= |x| < 2^64 --
+ * everything sum / count of two int64 can be; any other value is -ERANGE (*len = 0): it
+ * is never printed wrongly.  A null out or len is -EINVAL. */
+#define L5DH_DOUBLE_CHARS 26
+#define L5DH_LONG_CHARS 20
+int l5dh_format_double(double x, char* out /* >= L5DH_DOUBLE_CHARS */, size_t* len);
+int l5dh_format_long(int64_t v, char* out /* >= L5DH_LONG_CHARS */, size_t* len);
+int l5dh_format_ulong(uint64_t v, char* out /* >= L5DH_LONG_CHARS */, size_t* len);
+
+/* The Prometheus exposition of Stats, rendered on the device: the text is produced where
+ * the numbers are, and one buffer goes to whoever answers the scrape.  A name table holds
+ * what does not vary per scrape, fixed when a Stat is registered: row j < n prints element
+ * index[j] (index == NULL: j) of the value arrays under the escaped metric key
+ * key_bytes[key_off[j] .. key_off[j+1]) and the already-escaped text between the braces
+ * lab_bytes[lab_off[j] .. lab_off[j+1]) -- `a="b", c="d"`, possibly empty.  key_off and
+ * lab_off hold n + 1 ascending entries.  With lab = "" for an empty inner text, else
+ * `{inner}`, and an extra label appended as `{inner, quantile="0.5"}` (`{quantile="0.5"}`
+ * for an empty inner text), every line is `name[lab] value\n`.
+ *
+ * l5dh_render_summaries prints per row, from values[index[j]] (nvalues elements):
+ *   key_count lab N / key_sum lab N / key_avg lab D, then eight lines key{.. quantile="q"} N
+ *   for q = 0, 0.5, 0.9, 0.95, 0.99, 0.999, 0.9999, 1 (min, p50, p90, p95, p99, p9990,
+ *   p9999, max) -- N as l5dh_format_long, D as l5dh_format_double.
+ * l5dh_render_le prints per row, from le_rows[index[j]][0..ncuts] (what l5dh_le wrote) and
+ * sums[index[j]] (sums == NULL: 0), with the ncuts labels le[k]:
+ *   ncuts lines key_hist_bucket{.. le="<le[k]>"} n, one with le="+Inf" carrying the last
+ *   column, key_hist_sum lab s, key_hist_count lab <the last column> -- n as
+ *   l5dh_format_ulong.
+ *
+ * Every data pointer (the five arrays of the table included) may be host or device
+ * memory.  *len always receives the exact length of the text.  out == NULL is a size
+ * query (returns 0); out != NULL with cap < *len is -ERANGE and nothing is written;
+ * n == 0 writes nothing, sets *len = 0 and returns 0.  -EINVAL: ncuts outside
+ * [1, L5DH_LE_MAX], a null names, key_off, lab_off or le, nvalues == 0 (or null values)
+ * with n > 0.  Found on the device and reported by the call, l5dh_last_error naming the
+ * first such row, the output then unspecified: index[j] >= nvalues, offsets that descend,
+ * a row whose key and label text exceed 2^25 bytes (-EINVAL); an avg outside
+ * l5dh_format_double's domain (-ERANGE).  The calls read no engine state: they hold the
+ * context lock only to use its stream and scratch, and return once out is written. */
+typedef struct {
+  const uint32_t* index;     /* [n], nullable: row j prints element j */
+  const uint64_t* key_off;   /* [n + 1] */
+  const uint8_t* key_bytes;
+  const uint64_t* lab_off;   /* [n + 1] */
+  const uint8_t* lab_bytes;
+} l5dh_names;
+int l5dh_render_summaries(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const l5dh_summary* values,
+                          size_t nvalues, uint8_t* out, size_t cap, size_t* len);
+int l5dh_render_le(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const uint64_t* le_rows,
+                   const int64_t* sums /* nullable: 0 */, size_t nvalues, const int64_t* le, uint32_t ncuts,
+                   uint8_t* out, size_t cap, size_t* len);
+
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:
  *  - multi-process (or one thread per context): rank 0 calls l5dh_comm_unique_id,

@@ -42,6 +42,14 @@ PARAM_ROLLUP_ITEM = 14
 NO_GROUP = 0xFFFFFFFF  # L5DH_NO_GROUP
 MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
 LE_MAX = 64  # L5DH_LE_MAX
+DOUBLE_CHARS = 26  # L5DH_DOUBLE_CHARS
+LONG_CHARS = 20  # L5DH_LONG_CHARS
+
+
+class Names(ctypes.Structure):
+    """l5dh_names: the five arrays of a name table (host or device addresses; 0: NULL)."""
+    _fields_ = [("index", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("key_bytes", ctypes.c_void_p),
+                ("lab_off", ctypes.c_void_p), ("lab_bytes", ctypes.c_void_p)]
 
 MERGE_REDUCE_SCATTER = 0
 MERGE_ALL_REDUCE = 1
@@ -85,6 +93,13 @@ SIGNATURES = {
     "l5dh_le_cuts": (_c.c_int, [_vp, _c.c_size_t, _vp, _vp]),
     "l5dh_le": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int, _vp, _c.c_int]),
     "l5dh_le_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
+    "l5dh_format_double": (_c.c_int, [_c.c_double, _vp, _c.POINTER(_c.c_size_t)]),
+    "l5dh_format_long": (_c.c_int, [_c.c_int64, _vp, _c.POINTER(_c.c_size_t)]),
+    "l5dh_format_ulong": (_c.c_int, [_c.c_uint64, _vp, _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_summaries": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t,
+                                         _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_le": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _c.c_size_t,
+                                  _c.POINTER(_c.c_size_t)]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

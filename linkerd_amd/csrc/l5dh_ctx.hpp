@@ -16,6 +16,7 @@
 #include "l5dh_kernels.hpp"
 #include "l5dh_le.hpp"
 #include "l5dh_merge.hpp"
+#include "l5dh_render.hpp"
 #include "l5dh_rollup.hpp"
 
 namespace l5dh {
@@ -140,6 +141,9 @@ struct l5dh_ctx {
   // label rollups (l5dh_rollup.hip): the staged map, the plan's arrays, the partial rows, staged outputs
   DevBuf ru_group, ru_u32, ru_u64, ru_members, ru_igroup, ru_mlist, ru_partial, ru_tmp, ru_summ, ru_counts, ru_totals;
   DevBuf le_stage, le_sums_stage;  // cumulative `le` buckets (l5dh_le.hip): staged outputs
+  // the device renderer (l5dh_render.hip): staged names, values and output, the passes' scratch
+  DevBuf rd_index, rd_koff, rd_kbytes, rd_loff, rd_lbytes, rd_vals, rd_sums, rd_le, rd_out;
+  DevBuf rd_len, rd_offs, rd_avg, rd_flags, rd_tmp;
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params

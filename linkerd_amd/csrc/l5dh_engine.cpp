@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "l5dh_ctx.hpp"
+#include "l5dh_fmt.hpp"
 
 using namespace l5dh;
 
@@ -604,6 +605,102 @@ int do_le(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const
   return sync_stream(c);
 }
 
+// ---- the device renderer -----------------------------------------------------------
+// Bytes of a name array that is not used in place: its offsets' last entry (the write
+// pass, the only reader of the bytes, runs after every offset was found ascending).
+int rd_stage_bytes(l5dh_ctx* c, const uint8_t*& bytes, const uint64_t* off, size_t n, DevBuf& stage) {
+  if (direct(bytes, 1)) return 0;
+  uint64_t last = 0;
+  if (is_device_ptr(off)) {
+    HIPCHK(c, hipMemcpyAsync(&last, off + n, 8, hipMemcpyDeviceToHost, c->stream));
+    if (int r = sync_stream(c)) return r;
+  } else {
+    last = off[n];
+  }
+  if (last && !bytes) return fail(c, -EINVAL, "render: null name bytes under non-empty offsets");
+  return stage_in(c, bytes, (size_t)last, 1, stage);
+}
+
+// The findings of the passes, in the order the header lists them.
+int rd_findings(l5dh_ctx* c, const uint32_t* f) {
+  const uint32_t none = 0xFFFFFFFFu;
+  if (f[RF_BADIDX] != none)
+    return fail(c, -EINVAL, "render: index of row " + std::to_string(f[RF_BADIDX]) + " is not < nvalues");
+  if (f[RF_BADOFF] != none)
+    return fail(c, -EINVAL, "render: key_off or lab_off descends at row " + std::to_string(f[RF_BADOFF]));
+  if (f[RF_LONG] != none)
+    return fail(c, -EINVAL, "render: key and label text of row " + std::to_string(f[RF_LONG]) + " exceed 2^25 bytes");
+  if (f[RF_RANGE] != none)
+    return fail(c, -ERANGE,
+                "render: avg of row " + std::to_string(f[RF_RANGE]) + " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
+  if (f[RF_MISMATCH] != none)
+    return fail(c, -EIO, "internal: the render passes disagree on the length of row " + std::to_string(f[RF_MISMATCH]));
+  return 0;
+}
+
+// The passes over n > 0 rows; rows holds device pointers (the caller staged the values).
+// The caller holds the lock and has checked the arguments.
+template <class Rows>
+int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, const Rows& rows, uint8_t* out, size_t cap,
+              size_t* len) {
+  int r;
+  RenderNames nm{names->index, names->key_off, names->key_bytes, names->lab_off, names->lab_bytes};
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = rd_stage_bytes(c, nm.key_bytes, names->key_off, n, c->rd_kbytes)) ||
+        (r = rd_stage_bytes(c, nm.lab_bytes, names->lab_off, n, c->rd_lbytes)) ||
+        (r = stage_in(c, nm.index, n, 4, c->rd_index)) || (r = stage_in(c, nm.key_off, n + 1, 8, c->rd_koff)) ||
+        (r = stage_in(c, nm.lab_off, n + 1, 8, c->rd_loff)))
+      return r;
+  }
+  size_t tmp_bytes = 0;
+  HIPCHK(c, merge_count(nullptr, (uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  if ((r = ensure(c, c->rd_len, (n + 1) * 4)) || (r = ensure(c, c->rd_offs, (n + 1) * 8)) ||
+      (r = ensure(c, c->rd_flags, RF_WORDS * 4)) || (r = ensure(c, c->rd_tmp, tmp_bytes)))
+    return r;
+  uint32_t* flags = c->rd_flags.as<uint32_t>();
+  uint64_t* offs = c->rd_offs.as<uint64_t>();
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, hipMemsetAsync(flags, 0xFF, RF_WORDS * 4, c->stream));
+    HIPCHK(c, render_lengths(nm, (uint32_t)n, (uint32_t)nvalues, rows, c->rd_len.as<uint32_t>(), flags, c->stream));
+    HIPCHK(c, merge_count(nullptr, (uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
+  }
+  // the device's findings and the text's length: one host wait, before anything is written
+  uint32_t hf[RF_WORDS];
+  uint64_t total = 0;
+  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
+  if ((r = sync_stream(c)) || (r = rd_findings(c, hf))) return r;
+  if (len) *len = (size_t)total;
+  if (!out) return 0;  // a size query
+  if (cap < total)
+    return fail(c, -ERANGE, "render: the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
+  StagedOut<uint8_t> o;
+  if ((r = o.begin(c, out, (size_t)total, c->rd_out, 1))) return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, render_write(nm, (uint32_t)n, rows, offs, o.dev, flags, c->stream));
+  }
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = o.end(c))) return r;
+    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((r = sync_stream(c))) return r;
+  return rd_findings(c, hf);
+}
+
+// The arguments both render calls share.  0: go on; 1: n == 0, done; negative: an error.
+int rd_check(l5dh_ctx* c, const l5dh_names* names, size_t n, const void* values, size_t nvalues, size_t* len) {
+  if (len) *len = 0;
+  if (!names || !names->key_off || !names->lab_off) return fail(c, -EINVAL, "render: null names, key_off or lab_off");
+  if (n == 0) return 1;
+  if (nvalues == 0 || !values) return fail(c, -EINVAL, "render: no values for the rows");
+  if (n > 0xFFFFFFF0ull || nvalues > 0xFFFFFFFFull) return fail(c, -EINVAL, "render: more than 2^32 - 16 rows");
+  return 0;
+}
+
 }  // namespace
 
 l5dh_ctx::~l5dh_ctx() {
@@ -839,6 +936,58 @@ int l5dh_le_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, siz
   if (n == 0) return 0;
   if (!counts || !le_out) return fail(c, -EINVAL, "le: null dense rows or output");
   return do_le(c, 0, (uint32_t)n, counts, totals, lc, ncuts, le_out, sums_out, accumulate, nullptr, 0);
+}
+
+int l5dh_format_double(double x, char* out, size_t* len) {
+  if (!out || !len) return -EINVAL;
+  const int n = fmt::format_double(x, out);
+  *len = n < 0 ? 0 : (size_t)n;
+  return n < 0 ? -ERANGE : 0;
+}
+
+int l5dh_format_long(int64_t v, char* out, size_t* len) {
+  if (!out || !len) return -EINVAL;
+  *len = (size_t)fmt::format_long(v, out);
+  return 0;
+}
+
+int l5dh_format_ulong(uint64_t v, char* out, size_t* len) {
+  if (!out || !len) return -EINVAL;
+  *len = (size_t)fmt::format_ulong(v, out);
+  return 0;
+}
+
+int l5dh_render_summaries(l5dh_ctx* c, const l5dh_names* names, size_t n, const l5dh_summary* values, size_t nvalues,
+                          uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  int r = rd_check(c, names, n, values, nvalues, len);
+  if (r) return r < 0 ? r : 0;
+  const Summary88* v = reinterpret_cast<const Summary88*>(values);
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = stage_in(c, v, nvalues, 8, c->rd_vals))) return r;
+  }
+  if ((r = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT))) return r;
+  return do_render(c, names, n, nvalues, SummaryRows{v, c->rd_avg.as<uint8_t>()}, out, cap, len);
+}
+
+int l5dh_render_le(l5dh_ctx* c, const l5dh_names* names, size_t n, const uint64_t* le_rows, const int64_t* sums,
+                   size_t nvalues, const int64_t* le, uint32_t ncuts, uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (len) *len = 0;
+  if (ncuts < 1 || ncuts > L5DH_LE_MAX) return fail(c, -EINVAL, "render: ncuts must be in [1, 64]");
+  int r = rd_check(c, names, n, le_rows, nvalues, len);
+  if (r) return r < 0 ? r : 0;
+  if (!le) return fail(c, -EINVAL, "render: null le labels");
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = stage_in(c, le_rows, nvalues * ((size_t)ncuts + 1), 8, c->rd_vals)) ||
+        (r = stage_in(c, sums, nvalues, 8, c->rd_sums)) || (r = stage_in(c, le, (size_t)ncuts, 8, c->rd_le)))
+      return r;
+  }
+  return do_render(c, names, n, nvalues, LeRows{le_rows, sums, le, ncuts}, out, cap, len);
 }
 
 int l5dh_peek(l5dh_ctx* c, uint32_t series, l5dh_bucket_count* out, size_t cap, size_t* n_out) {

@@ -1,0 +1,319 @@
+// l5dh_render.hip -- the Prometheus text of Stats, produced where the numbers are.
+//
+// A row's block is a list of lines, each
+//     key sfx [ `{` inner [`, `] ext ev `"` `}` ] ` ` number `\n`
+// with key / inner the row's name bytes, sfx / ext / ev small constant texts (or, for ev,
+// an `le` label) and number a Java long, an unsigned 64-bit decimal or the avg's
+// Double.toString.  prometheus.py's write_metrics, write_rollup_metrics and
+// write_histogram_metrics print exactly these lines.
+//
+//   k_rd_len    a lane per row: checks the row (index, offsets, name length), formats its
+//               avg once into the row's 32-byte slot, and adds up the lines' lengths from
+//               the name lengths and the digit counts.
+//   (scan)      the fleet merge's exclusive u32 -> u64 scan (merge_count).
+//   k_rd_write  a wave per row (one-wave workgroups striding over the rows).  Lane t lays
+//               out line t: a wave scan of the line lengths gives its place, and the lane
+//               writes the line's own small pieces (sfx, braces, ext, numbers).  The wave
+//               then copies key and inner into every line together (their first 64 bytes
+//               from registers).  A row of at most RD_STAGE bytes is built in LDS at the
+//               destination's offset within 16 bytes, so it leaves as aligned 16-byte
+//               stores between a byte-wise head and tail; a longer row is built by the same
+//               code straight in the output.  Only row j's wave writes row j's bytes.
+#include "l5dh_device.hpp"
+#include "l5dh_fmt.hpp"
+#include "l5dh_render.hpp"
+
+namespace l5dh {
+namespace {
+
+constexpr uint32_t RD_STAGE = 4096;               // bytes of a row built in LDS
+constexpr uint32_t RD_LINES_MAX = LE_MAX + 3;     // K buckets, +Inf, _sum, _count
+constexpr uint32_t RD_GRID_MAX = 256 * 32;        // one-wave workgroups of the write pass
+
+enum { NUM_LONG = 0, NUM_ULONG = 1, NUM_TEXT = 2 };
+
+struct Line {
+  const char* sfx;      // after the key
+  uint32_t sfx_n;
+  const char* ext;      // the extra label up to its value's opening quote (ext_n == 0: none)
+  uint32_t ext_n;
+  const char* ev;       // the extra label's value, or null: the long ev_num
+  uint32_t ev_n;
+  int64_t ev_num;
+  uint32_t kind;        // NUM_*
+  uint64_t v;           // NUM_LONG (its bits) / NUM_ULONG
+  const uint8_t* text;  // NUM_TEXT
+  uint32_t text_n;
+};
+
+__device__ __forceinline__ uint32_t num_len(const Line& L) {
+  return L.kind == NUM_TEXT ? L.text_n : (uint32_t)(L.kind == NUM_LONG ? fmt::long_digits((int64_t)L.v) : fmt::ulong_digits(L.v));
+}
+__device__ __forceinline__ uint32_t ev_len(const Line& L) { return L.ev ? L.ev_n : (uint32_t)fmt::long_digits(L.ev_num); }
+
+// Bytes of the line up to its inner text (key, sfx, `{`) and in all.
+__device__ __forceinline__ uint32_t line_head(uint32_t klen, uint32_t ilen, const Line& L) {
+  return klen + L.sfx_n + ((ilen || L.ext_n) ? 1u : 0u);
+}
+__device__ __forceinline__ uint32_t line_len(uint32_t klen, uint32_t ilen, const Line& L) {
+  uint32_t n = line_head(klen, ilen, L) + ilen;
+  if (L.ext_n) n += (ilen ? 2u : 0u) + L.ext_n + ev_len(L) + 1u;  // [`, `] ext ev `"`
+  if (ilen || L.ext_n) n += 1u;                                    // `}`
+  return n + 1u + num_len(L) + 1u;                                 // ` ` number `\n`
+}
+
+template <class S>
+__device__ __forceinline__ uint32_t put(uint8_t* dst, uint32_t p, const S* s, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) dst[p + i] = (uint8_t)s[i];
+  return p + n;
+}
+
+// The lane's own pieces of its line at dst + pos: everything but key and inner.  Writes
+// inside [pos, pos + line_len) only, and ends exactly there.
+__device__ __forceinline__ void line_write(uint8_t* dst, uint32_t pos, uint32_t klen, uint32_t ilen, const Line& L) {
+  uint32_t p = put(dst, pos + klen, L.sfx, L.sfx_n);
+  if (ilen || L.ext_n) dst[p++] = '{';
+  p += ilen;
+  if (L.ext_n) {
+    if (ilen) {
+      dst[p++] = ',';
+      dst[p++] = ' ';
+    }
+    p = put(dst, p, L.ext, L.ext_n);
+    if (L.ev)
+      p = put(dst, p, L.ev, L.ev_n);
+    else
+      p += (uint32_t)fmt::format_long(L.ev_num, dst + p);
+    dst[p++] = '"';
+  }
+  if (ilen || L.ext_n) dst[p++] = '}';
+  dst[p++] = ' ';
+  if (L.kind == NUM_TEXT)
+    p = put(dst, p, L.text, L.text_n);
+  else if (L.kind == NUM_LONG)
+    p += (uint32_t)fmt::format_long((int64_t)L.v, dst + p);
+  else
+    p += (uint32_t)fmt::format_ulong(L.v, dst + p);
+  dst[p] = '\n';
+}
+
+// ---- the two blocks ---------------------------------------------------------------
+// Summary: _count, _sum, _avg, then QUANTILES' eight lines (min, p50, .., p9999, max).
+struct SummaryBlock {
+  SummaryRows r;
+  __device__ __forceinline__ uint32_t nlines() const { return 11u; }
+  // The length pass's own work for row j (value idx): the avg's text.  False: out of domain.
+  __device__ __forceinline__ bool prepare(uint32_t j, uint32_t idx) const {
+    uint8_t* slot = r.avg + (size_t)j * RENDER_AVG_SLOT;
+    const int n = fmt::format_double(r.v[idx].avg, slot);
+    slot[RENDER_AVG_SLOT - 1] = (uint8_t)(n < 0 ? 0 : n);
+    return n >= 0;
+  }
+  __device__ __forceinline__ void line(uint32_t j, uint32_t idx, uint32_t t, Line& L) const {
+    // Summary88's words: count, min, max, sum, p50, p90, p95, p99, p9990, p9999
+    const uint32_t field = t == 0 ? 0u : (t == 1 ? 3u : (t == 3 ? 1u : (t == 10 ? 2u : t)));
+    L.sfx = t == 0 ? "_count" : (t == 1 ? "_sum" : "_avg");
+    L.sfx_n = t == 0 ? 6u : (t < 3 ? 4u : 0u);
+    L.ext = "quantile=\"";
+    L.ext_n = t < 3 ? 0u : 10u;
+    const char* q = "0      0.5    0.9    0.95   0.99   0.999  0.9999 1";  // 7 bytes apart
+    const uint32_t qi = t < 3 ? 0u : t - 3u;
+    L.ev = q + 7u * qi;
+    L.ev_n = (0x16544331u >> (4u * qi)) & 15u;  // their lengths: 1 3 3 4 4 5 6 1
+    L.ev_num = 0;
+    const uint8_t* slot = r.avg + (size_t)j * RENDER_AVG_SLOT;
+    L.kind = t == 2 ? NUM_TEXT : NUM_LONG;
+    L.v = t == 2 ? 0ull : (uint64_t)reinterpret_cast<const int64_t*>(r.v + idx)[field];
+    L.text = slot;
+    L.text_n = t == 2 ? slot[RENDER_AVG_SLOT - 1] : 0u;
+  }
+};
+
+// Histogram: K `_hist_bucket` lines with le="<label>", the le="+Inf" line, _hist_sum, _hist_count.
+struct LeBlock {
+  LeRows r;
+  __device__ __forceinline__ uint32_t nlines() const { return r.K + 3u; }
+  __device__ __forceinline__ bool prepare(uint32_t, uint32_t) const { return true; }
+  __device__ __forceinline__ void line(uint32_t, uint32_t idx, uint32_t t, Line& L) const {
+    const uint32_t K = r.K;
+    const uint64_t* row = r.le_rows + (size_t)idx * (K + 1u);
+    L.sfx = t <= K ? "_hist_bucket" : (t == K + 1u ? "_hist_sum" : "_hist_count");
+    L.sfx_n = t <= K ? 12u : (t == K + 1u ? 9u : 11u);
+    L.ext = "le=\"";
+    L.ext_n = t <= K ? 4u : 0u;
+    L.ev = t == K ? "+Inf" : nullptr;
+    L.ev_n = t == K ? 4u : 0u;
+    L.ev_num = t < K ? r.le[t] : 0;
+    L.kind = t == K + 1u ? NUM_LONG : NUM_ULONG;
+    L.v = t == K + 1u ? (r.sums ? (uint64_t)r.sums[idx] : 0ull) : row[t < K ? t : K];
+    L.text = nullptr;
+    L.text_n = 0u;
+  }
+};
+
+// ---- length pass ------------------------------------------------------------------
+template <class Block>
+__global__ __launch_bounds__(256) void k_rd_len(RenderNames nm, uint32_t n, uint32_t nvalues, Block blk,
+                                                uint32_t* __restrict__ len, uint32_t* __restrict__ flags) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t idx = nm.index ? nm.index[j] : j;
+  const uint64_t k0 = nm.key_off[j], k1 = nm.key_off[j + 1], i0 = nm.lab_off[j], i1 = nm.lab_off[j + 1];
+  bool ok = true;
+  if (idx >= nvalues) {
+    atomicMin(flags + RF_BADIDX, j);
+    ok = false;
+  }
+  if (k1 < k0 || i1 < i0) {
+    atomicMin(flags + RF_BADOFF, j);
+    ok = false;
+  } else if (k1 - k0 > RENDER_NAME_MAX || i1 - i0 > RENDER_NAME_MAX || (k1 - k0) + (i1 - i0) > RENDER_NAME_MAX) {
+    atomicMin(flags + RF_LONG, j);
+    ok = false;
+  }
+  if (ok && !blk.prepare(j, idx)) {
+    atomicMin(flags + RF_RANGE, j);
+    ok = false;
+  }
+  uint32_t total = 0u;
+  if (ok) {
+    const uint32_t klen = (uint32_t)(k1 - k0), ilen = (uint32_t)(i1 - i0), nl = blk.nlines();
+    for (uint32_t t = 0; t < nl; ++t) {
+      Line L;
+      blk.line(j, idx, t, L);
+      total += line_len(klen, ilen, L);
+    }
+  }
+  len[j] = total;
+}
+
+// ---- write pass -------------------------------------------------------------------
+// len bytes of src at dst, the wave together; pre = src[lane] (lanes < len).
+__device__ __forceinline__ void emit(uint8_t* dst, const uint8_t* __restrict__ src, uint32_t len, uint8_t pre,
+                                     uint32_t lane) {
+  if (lane < len) dst[lane] = pre;
+  for (uint32_t i = lane + 64u; i < len; i += 64u) dst[i] = src[i];
+}
+
+// Builds the row at dst (LDS or the output: the same code, inlined for each).  False: the
+// lines add up to another length than rowlen, and nothing was written.
+template <class Block>
+__device__ __forceinline__ bool build_row(uint8_t* dst, const Block& blk, uint32_t j, uint32_t idx,
+                                          const uint8_t* __restrict__ key, uint32_t klen,
+                                          const uint8_t* __restrict__ inner, uint32_t ilen, uint32_t rowlen,
+                                          uint32_t* lpos, uint32_t* ipos, uint32_t lane) {
+  const uint32_t nl = blk.nlines();
+  // every line's place first: nothing is written before the total is known to match
+  uint32_t cursor = 0u;
+  for (uint32_t base = 0; base < nl; base += 64u) {  // (wave-uniform bounds)
+    const uint32_t t = base + lane;
+    Line L;
+    uint32_t ln = 0u;
+    if (t < nl) {
+      blk.line(j, idx, t, L);
+      ln = line_len(klen, ilen, L);
+    }
+    const uint32_t incl = wave_incl_scan32(ln);
+    if (t < nl) {
+      lpos[t] = cursor + incl - ln;
+      ipos[t] = cursor + incl - ln + line_head(klen, ilen, L);
+    }
+    cursor += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  }
+  if (cursor != rowlen) return false;
+  __syncthreads();  // (one wave: orders lpos / ipos)
+  for (uint32_t base = 0; base < nl; base += 64u) {
+    const uint32_t t = base + lane;
+    if (t < nl) {
+      Line L;
+      blk.line(j, idx, t, L);
+      line_write(dst, lpos[t], klen, ilen, L);
+    }
+  }
+  const uint8_t kpre = lane < klen ? key[lane] : (uint8_t)0, ipre = lane < ilen ? inner[lane] : (uint8_t)0;
+  for (uint32_t t = 0; t < nl; ++t) {
+    emit(dst + lpos[t], key, klen, kpre, lane);
+    emit(dst + ipos[t], inner, ilen, ipre, lane);
+  }
+  return true;
+}
+
+template <class Block>
+__global__ __launch_bounds__(64) void k_rd_write(RenderNames nm, uint32_t n, Block blk,
+                                                 const uint64_t* __restrict__ offs, uint8_t* __restrict__ out,
+                                                 uint32_t* __restrict__ flags) {
+  __shared__ uint4 stage4[RD_STAGE / 16 + 1];  // (+16 bytes: the destination's offset within 16)
+  __shared__ uint32_t lpos[RD_LINES_MAX], ipos[RD_LINES_MAX];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {  // (wave-uniform)
+    const uint32_t idx = nm.index ? nm.index[j] : j;
+    const uint64_t k0 = nm.key_off[j], i0 = nm.lab_off[j], o0 = offs[j];
+    const uint32_t klen = (uint32_t)(nm.key_off[j + 1] - k0), ilen = (uint32_t)(nm.lab_off[j + 1] - i0);
+    const uint32_t rowlen = (uint32_t)(offs[j + 1] - o0);
+    const uint8_t* key = nm.key_bytes + k0;
+    const uint8_t* inner = nm.lab_bytes + i0;
+    uint8_t* gdst = out + o0;
+    bool ok;
+    if (rowlen <= RD_STAGE) {
+      const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(gdst) & 15u);
+      uint8_t* sdst = reinterpret_cast<uint8_t*>(stage4) + skew;
+      ok = build_row(sdst, blk, j, idx, key, klen, inner, ilen, rowlen, lpos, ipos, lane);
+      __syncthreads();
+      if (ok) {
+        // head up to the first 16-byte boundary of the output, aligned 16-byte body, tail
+        const uint32_t head = min(rowlen, (16u - skew) & 15u);
+        if (lane < head) gdst[lane] = sdst[lane];
+        const uint32_t body = (rowlen - head) >> 4;
+        const uint4* s4 = reinterpret_cast<const uint4*>(sdst + head);  // (skew + head is a multiple of 16, or body == 0)
+        uint4* g4 = reinterpret_cast<uint4*>(gdst + head);
+        for (uint32_t i = lane; i < body; i += 64u) g4[i] = s4[i];
+        const uint32_t done = head + (body << 4);
+        if (done + lane < rowlen) gdst[done + lane] = sdst[done + lane];  // (< 16 bytes)
+      }
+    } else {
+      ok = build_row(gdst, blk, j, idx, key, klen, inner, ilen, rowlen, lpos, ipos, lane);
+    }
+    if (!ok && lane == 0) atomicMin(flags + RF_MISMATCH, j);
+    __syncthreads();  // the stage and the places are reused by the next row
+  }
+}
+
+template <class Block>
+hipError_t lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const Block& blk, uint32_t* len, uint32_t* flags,
+                   hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rd_len<Block>, dim3((n + 255u) / 256u), dim3(256), 0, st, nm, n, nvalues, blk, len, flags);
+  return hipGetLastError();
+}
+
+template <class Block>
+hipError_t write(const RenderNames& nm, uint32_t n, const Block& blk, const uint64_t* offs, uint8_t* out, uint32_t* flags,
+                 hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rd_write<Block>, dim3(n < RD_GRID_MAX ? n : RD_GRID_MAX), dim3(64), 0, st, nm, n, blk, offs, out,
+                     flags);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const SummaryRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  return lengths(nm, n, nvalues, SummaryBlock{rows}, len, flags, st);
+}
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const LeRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
+  return lengths(nm, n, nvalues, LeBlock{rows}, len, flags, st);
+}
+hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  return write(nm, n, SummaryBlock{rows}, offs, out, flags, st);
+}
+hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
+  return write(nm, n, LeBlock{rows}, offs, out, flags, st);
+}
+
+}  // namespace l5dh

@@ -1,0 +1,60 @@
+// l5dh_render.hpp -- the Prometheus exposition of Stats, rendered on the device
+// (l5dh_render.hip): per row of a name table the summary block or the `_hist` block,
+// byte for byte what linkerd_amd/prometheus.py prints.
+#pragma once
+
+#include "l5dh_kernels.hpp"
+#include "l5dh_le.hpp"
+
+namespace l5dh {
+
+// The name table (device pointers): row j prints element index[j] (null: j) of the value
+// arrays under the escaped key key_bytes[key_off[j] .. key_off[j+1]) and the escaped text
+// between the braces lab_bytes[lab_off[j] .. lab_off[j+1]) (may be empty).
+struct RenderNames {
+  const uint32_t* index;
+  const uint64_t* key_off;
+  const uint8_t* key_bytes;
+  const uint64_t* lab_off;
+  const uint8_t* lab_bytes;
+};
+
+// The flag words of a call: each the least row with that finding (0xFFFFFFFF: none).
+enum {
+  RF_BADIDX = 0,    // index[j] >= nvalues
+  RF_BADOFF = 1,    // key_off or lab_off descends at row j
+  RF_RANGE = 2,     // the row's avg is outside the formatter's domain
+  RF_LONG = 3,      // key + label text above RENDER_NAME_MAX bytes (a row would pass 2^32 bytes)
+  RF_MISMATCH = 4,  // the write pass laid a row out to another length than the length pass (internal)
+  RF_WORDS = 8
+};
+// 67 lines (L5DH_LE_MAX cuts) of a name this long, their fixed text and numbers stay below 2^32.
+constexpr uint64_t RENDER_NAME_MAX = 1ull << 25;
+constexpr uint32_t RENDER_AVG_SLOT = 32;  // per row: the avg text (26 bytes at most), its length in the last byte
+
+// The values of a call (device pointers).
+struct SummaryRows {
+  const Summary88* v;  // [nvalues]
+  uint8_t* avg;        // [n][RENDER_AVG_SLOT]: written by the length pass, read by the write pass
+};
+struct LeRows {
+  const uint64_t* le_rows;  // [nvalues][K + 1]
+  const int64_t* sums;      // [nvalues], nullable: 0
+  const int64_t* le;        // [K] the labels
+  uint32_t K;
+};
+
+// Length pass: len[j] = bytes of row j's block for j < n (a row with a finding: 0, and its
+// flag word is lowered).  flags must hold 0xFFFFFFFF words.
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const SummaryRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st);
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const LeRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st);
+// Write pass: row j's block at out + offs[j] (offs: the exclusive prefix of len, offs[n] the
+// total).  Only launched when the length pass raised no flag: it trusts the table.
+hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st);
+hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st);
+
+}  // namespace l5dh

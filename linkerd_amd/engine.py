@@ -16,6 +16,7 @@ their inputs; calls with device outputs return once the outputs are written.
 from __future__ import annotations
 
 import ctypes
+import errno
 from typing import Optional, Sequence
 
 import numpy as np
@@ -24,6 +25,9 @@ from . import _native as N
 
 _NP_OF_TORCH = {"torch.int32": np.int32, "torch.uint32": np.uint32, "torch.int64": np.int64, "torch.uint64": np.uint64,
                 "torch.float32": np.float32, "torch.float64": np.float64, "torch.uint8": np.uint8}
+
+
+QUERY = object()  # render_summaries / render_le: out=QUERY asks for the text's length only
 
 
 def _is_torch(x) -> bool:
@@ -47,6 +51,7 @@ class HistogramEngine:
         self.device = int(device)
         self._stream = None  # external stream handle the context runs on (None: its own)
         self._events = []
+        self._render_cap = {}  # bytes of the last text of each render call
         self.nranks, self.rank = 1, 0
 
     # -- lifecycle -----------------------------------------------------------
@@ -399,6 +404,79 @@ class HistogramEngine:
         le, sums = np.zeros((n, K + 1), np.uint64), np.zeros(n, np.int64)
         self.le_counts_into(cuts, le, sums, dense=(counts, totals))
         return le, sums
+
+    # -- Prometheus text on the device ------------------------------------------------
+    def _names(self, names) -> "N.Names":
+        """The l5dh_names of a prometheus.NameTable (numpy arrays, or torch tensors on the
+        engine's GPU): every array checked as every other buffer is."""
+        n = names.n
+        return N.Names(self._buf(names.index, (np.uint32, np.int32), "names.index", n),
+                       self._buf(names.key_off, (np.uint64, np.int64), "names.key_off", n + 1),
+                       self._buf(names.key_bytes, (np.uint8,), "names.key_bytes"),
+                       self._buf(names.lab_off, (np.uint64, np.int64), "names.lab_off", n + 1),
+                       self._buf(names.lab_bytes, (np.uint8,), "names.lab_bytes"))
+
+    def _render(self, call, where: str, out):
+        """Runs call(out pointer, cap, byref(len)): into ``out`` (a uint8 buffer; returns
+        the length), or into a host buffer of the right size (returns bytes).  The size of
+        the last text is tried first, so a steady scrape takes one call, not a query and a
+        call."""
+        ln = ctypes.c_size_t(0)
+        if out is QUERY:
+            self._check(call(None, 0, ctypes.byref(ln)), where)
+            return ln.value
+        if out is not None:
+            op = self._buf(out, (np.uint8,), "out", writable=True)
+            self._check(call(op, _numel(out), ctypes.byref(ln)), where)
+            return ln.value
+        cap = self._render_cap.get(where, 0)
+        while True:
+            buf = np.empty(cap, np.uint8) if cap else None
+            rc = call(None if buf is None else buf.ctypes.data, cap, ctypes.byref(ln))
+            if rc == 0 and (buf is not None or ln.value == 0):
+                self._render_cap[where] = ln.value
+                return b"" if buf is None else buf[:ln.value].tobytes()
+            if rc == 0 or (rc == -errno.ERANGE and ln.value > cap):
+                cap = ln.value  # the size query's answer, or what the text outgrew
+                continue
+            self._check(rc, where)
+
+    def render_summaries(self, names, values, out=None):
+        """The summary blocks (``_count``, ``_sum``, ``_avg``, eight quantile lines) of
+        the rows of ``names`` (prometheus.NameTable) from ``values``: summaries as the
+        numpy summary dtype or int64 [nvalues*11], host or device; row j prints element
+        names.index[j] (index None: j).  Byte for byte prometheus.write_metrics' lines.
+        Returns bytes, or with ``out`` (a uint8 numpy array or torch tensor on the
+        engine's GPU) writes there and returns the length; out=QUERY writes nothing and
+        returns the length the text would have."""
+        if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
+            if not values.flags["C_CONTIGUOUS"]:
+                raise ValueError("values: needs contiguous summary records")
+            vp, nvalues = values.ctypes.data, int(values.size)
+        else:
+            vp, nvalues = self._buf(values, (np.int64,), "values"), _numel(values) // 11
+        nm, n = self._names(names), names.n
+        return self._render(lambda op, cap, ln: self._lib.l5dh_render_summaries(
+            self._ctx, ctypes.byref(nm), n, vp, nvalues, op, cap, ln), "l5dh_render_summaries", out)
+
+    def render_le(self, names, le_rows, sums, le_labels, out=None):
+        """The ``_hist`` blocks (K ``_hist_bucket`` lines, ``le="+Inf"``, ``_hist_sum``,
+        ``_hist_count``) of the rows of ``names`` from le_rows uint64 (or int64)
+        [nvalues][K+1], sums int64 [nvalues] (None: 0) and the K labels ``le_labels``
+        (int64) -- what le_counts / le_cuts return.  Byte for byte
+        prometheus.write_histogram_metrics' lines.  Returns as render_summaries does."""
+        if not _is_torch(le_labels):
+            le_labels = np.ascontiguousarray(np.asarray(le_labels, np.int64).reshape(-1))
+        K = _numel(le_labels)
+        lp = self._buf(le_labels, (np.int64,), "le_labels")
+        nvalues = _numel(le_rows) // (K + 1)
+        if nvalues * (K + 1) != _numel(le_rows):
+            raise ValueError("le_rows must hold whole rows of K + 1 counts")
+        rp = self._buf(le_rows, (np.uint64, np.int64), "le_rows")
+        sp = self._buf(sums, (np.int64,), "sums", nvalues)
+        nm, n = self._names(names), names.n
+        return self._render(lambda op, cap, ln: self._lib.l5dh_render_le(
+            self._ctx, ctypes.byref(nm), n, rp, sp, nvalues, lp, K, op, cap, ln), "l5dh_render_le", out)
 
     # -- fleet merge (RCCL) ------------------------------------------------------
     @staticmethod

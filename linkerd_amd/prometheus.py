@@ -14,6 +14,8 @@ from __future__ import annotations
 import re
 from typing import List, Sequence, Tuple
 
+import numpy as np
+
 from .javafmt import double_to_string, float_to_string, long_to_string
 from .telemetry import Metric, MetricsTree
 
@@ -110,6 +112,126 @@ def write_histogram_metrics(tree: MetricsTree, engine, out: List[str], prefix0: 
         write_histogram_metrics(child, engine, out, prefix1 + (name,), labels1)
 
 
+NO_INDEX = 0xFFFFFFFF  # NameTable.index of a Stat without a series id (no device call takes such a row)
+
+
+def label_text(labels: Labels) -> str:
+    """The text between the braces of format_labels(labels) ("" for no labels)."""
+    return ", ".join(f'{escape_label_key(k)}="{escape_label_val(v)}"' for k, v in labels)
+
+
+class NameTable:
+    """What the device renderer (HistogramEngine.render_summaries / render_le) needs of
+    the names, none of which varies per scrape: per row the escaped metric key and the
+    escaped text between the braces, as UTF-8 bytes behind n + 1 offsets, and ``index``,
+    the element of the value arrays the row prints (None: the row's own number).
+    ``metrics`` (host tables of a tree) are the rows' Stats."""
+
+    def __init__(self, index, key_off, key_bytes, lab_off, lab_bytes, metrics=None):
+        self.index, self.key_off, self.key_bytes = index, key_off, key_bytes
+        self.lab_off, self.lab_bytes, self.metrics = lab_off, lab_bytes, metrics
+
+    @property
+    def n(self) -> int:
+        return int(self.key_off.shape[0]) - 1
+
+    @staticmethod
+    def build(keys: Sequence[str], inners: Sequence[str], index=None, metrics=None) -> "NameTable":
+        def pack(texts):
+            enc = [t.encode("utf-8") for t in texts]
+            off = np.zeros(len(enc) + 1, np.uint64)
+            off[1:] = np.cumsum(np.asarray([len(b) for b in enc], np.uint64))
+            return off, np.frombuffer(b"".join(enc), np.uint8).copy()
+        key_off, key_bytes = pack(keys)
+        lab_off, lab_bytes = pack(inners)
+        if index is not None:
+            index = np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint32))
+        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics)
+
+    def take(self, rows) -> "NameTable":
+        """The table of the given rows, in that order (a host table)."""
+        rows = np.asarray(rows, np.int64)
+
+        def gather(off, data):
+            start = off[rows].astype(np.int64)
+            length = off[rows + 1].astype(np.int64) - start
+            new = np.zeros(rows.size + 1, np.uint64)
+            new[1:] = np.cumsum(length.astype(np.uint64))
+            src = np.repeat(start - new[:-1].astype(np.int64), length) + np.arange(int(new[-1]), dtype=np.int64)
+            return new, data[src]
+        key_off, key_bytes = gather(self.key_off, self.key_bytes)
+        lab_off, lab_bytes = gather(self.lab_off, self.lab_bytes)
+        index = None if self.index is None else self.index[rows]
+        metrics = None if self.metrics is None else [self.metrics[int(r)] for r in rows]
+        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics)
+
+    def to_device(self, device: int = 0) -> "NameTable":
+        """The same table in device memory (torch tensors): uploaded once, reused by
+        every scrape."""
+        import torch
+        dev = torch.device("cuda", int(device))
+
+        def up(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a)
+            # (the same bits under torch's long-standing signed types)
+            a = a.view({8: np.int64, 4: np.int32}.get(a.dtype.itemsize, np.uint8)) if a.dtype.kind == "u" else a
+            return torch.from_numpy(a).to(dev)
+        return NameTable(up(self.index), up(self.key_off), up(self.key_bytes), up(self.lab_off), up(self.lab_bytes),
+                         self.metrics)
+
+
+def stat_name_table(tree: MetricsTree) -> NameTable:
+    """The name table of the Stats of ``tree``, walked exactly as write_metrics walks it
+    (the same prefix rewrite, escapes and child order): one row per Stat in DFS order,
+    ``index`` its series id (NO_INDEX for a Stat without one)."""
+    keys: List[str] = []
+    inners: List[str] = []
+    index: List[int] = []
+    metrics: list = []
+
+    def visit(t: MetricsTree, prefix0: Tuple[str, ...], labels0: Labels) -> None:
+        prefix1, labels1 = _rewrite(prefix0, labels0)
+        m = t.metric
+        if isinstance(m, Metric.Stat):
+            keys.append(escape_key(":".join(prefix1)))
+            inners.append(label_text(labels1))
+            index.append(NO_INDEX if m.series_id is None else int(m.series_id))
+            metrics.append(m)
+        for name, child in t.children.items():
+            visit(child, prefix1 + (name,), labels1)
+
+    visit(tree, (), ())
+    return NameTable.build(keys, inners, index, metrics)
+
+
+def rollup_name_table(plan) -> NameTable:
+    """The name table of a rollup.RollupPlan's groups: row g prints group g (no index)."""
+    return NameTable.build([key for key, _ in plan.groups], [label_text(labels) for _, labels in plan.groups])
+
+
+def summary_records(summaries) -> np.ndarray:
+    """HistogramSummary objects as the engine's summary records."""
+    from ._native import SUMMARY_DTYPE, SUMMARY_FIELDS
+    out = np.zeros(len(summaries), SUMMARY_DTYPE)
+    for f in SUMMARY_FIELDS:
+        out[f] = [getattr(s, f) for s in summaries]
+    return out
+
+
+def write_scalar_metrics(tree: MetricsTree, out: List[str], prefix0: Tuple[str, ...] = (), labels0: Labels = ()) -> None:
+    """write_metrics' counter and gauge lines alone (the values the engine does not hold)."""
+    prefix1, labels1 = _rewrite(prefix0, labels0)
+    m = tree.metric
+    if isinstance(m, Metric.Counter):
+        out.append(f"{escape_key(':'.join(prefix1))}{format_labels(labels1)} {long_to_string(m.get())}\n")
+    elif isinstance(m, Metric.Gauge):
+        out.append(f"{escape_key(':'.join(prefix1))}{format_labels(labels1)} {float_to_string(m.get())}\n")
+    for name, child in tree.children.items():
+        write_scalar_metrics(child, out, prefix1 + (name,), labels1)
+
+
 class PrometheusTelemeter:
     """PrometheusTelemeter (PrometheusTelemeter.scala:17-35): /admin/metrics/prometheus."""
 
@@ -134,6 +256,53 @@ class PrometheusTelemeter:
         if self.histograms is not None:
             write_histogram_metrics(self.metrics, self.histograms, out)
         return "".join(out)
+
+    def render_bytes(self, engine, names: "NameTable" = None, summaries=None) -> bytes:
+        """The exposition as bytes, the Stats' text rendered on the device by ``engine``
+        (a HistogramEngine): the counter and gauge lines (printed here: the engine does
+        not hold them), the Stat blocks, the rollup blocks if ``rollups`` is set, the
+        ``_hist`` blocks if ``histograms`` is set.  As a line multiset this is render().
+        ``names``: stat_name_table(self.metrics) kept by the caller (host memory, or
+        to_device() for the device calls); built here when None.  ``summaries``: the
+        snapshot's records indexed by series id, host or device (every Stat of the table
+        then prints its record); None takes each Stat's snapshotted summary, and a Stat
+        without one prints nothing."""
+        out: List[str] = []
+        write_scalar_metrics(self.metrics, out)
+        parts = ["".join(out).encode("utf-8")]
+        table = stat_name_table(self.metrics) if names is None else names
+        host = table if table.metrics is not None and isinstance(table.key_off, np.ndarray) else None
+        if summaries is not None:
+            if table.n:
+                parts.append(engine.render_summaries(table, summaries))
+        else:
+            if host is None:
+                host = stat_name_table(self.metrics)
+            snaps = [m.snapshotted_summary for m in host.metrics]
+            rows = [j for j, s in enumerate(snaps) if s is not None]
+            if rows:
+                # the kept rows in table order with their records beside them: no index
+                shown = host if len(rows) == host.n else host.take(rows)
+                shown = NameTable(None, shown.key_off, shown.key_bytes, shown.lab_off, shown.lab_bytes, shown.metrics)
+                parts.append(engine.render_summaries(shown, summary_records([snaps[j] for j in rows])))
+        if self.rollups is not None:
+            plan, group_summaries = self.rollups
+            k = min(plan.ngroups, len(group_summaries))
+            if k:
+                groups = rollup_name_table(plan)
+                groups = groups if k == groups.n else groups.take(range(k))
+                parts.append(engine.render_summaries(groups, summary_records(list(group_summaries)[:k])))
+        h = self.histograms
+        if h is not None and h.le_cuts is not None and table.n:
+            # write_histogram_metrics prints every Stat that holds a series id
+            live = table
+            if table.metrics is not None and any(m.series_id is None for m in table.metrics):
+                if host is None:
+                    host = stat_name_table(self.metrics)
+                live = host.take([j for j, m in enumerate(host.metrics) if m.series_id is not None])
+            if live.n:
+                parts.append(engine.render_le(live, h.le_buckets, h.le_sums, h.le_labels))
+        return b"".join(parts)
 
 
 def line_multiset(text: str) -> dict:
