@@ -93,7 +93,7 @@ struct l5dh_ctx {
   Arr<uint32_t> d_enc_base;  // [F] sparse export: each tile's first word of the unpacked encoding
   Arr<uint32_t> d_enc_h0;    // [F] sparse export: words reserved for half 0 of a big or dirty tile
   Arr<uint32_t> d_enc_dw;    // [2F] sparse export: words of each half of a dirty tile's state rows
-  uint32_t* h_header = nullptr;      // pinned: [4] ingest error count (written by k_rfix1), [5] big tiles of the last plan
+  uint32_t* h_header = nullptr;      // pinned: [PIN_ERR] ingest error count (written by k_rfix1), [PIN_BIG] big tiles of the last plan
   uint32_t* h_header_dev = nullptr;  // its device-side address
   Arr<uint32_t> d_kest;   // [2F] sampled ids per (tile, half) key of the batch being binned
   Arr<uint32_t> d_kprev;  // [2F] exact records per key of the previous batch (region sizes)
@@ -123,7 +123,7 @@ struct l5dh_ctx {
   hipEvent_t tick_ev[NTICK] = {};
   uint64_t tick_of[NTICK] = {};
   uint64_t tick_next = 0, tick_done = 0;
-  uint32_t err_reported = 0;  // invalid-id reports already returned (h_header[4] is the device's count)
+  uint32_t err_reported = 0;  // invalid-id reports already returned (h_header[PIN_ERR] is the device's count)
   // fleet merge (RCCL)
   ncclComm_t comm = nullptr;
   int nranks = 1, rank = 0;

@@ -74,7 +74,8 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t x) {  // every lane gets t
 // also owns 1792..1797 (groups 7 and 8; group 8 = bins 1796, 1797 + padding).
 __device__ __forceinline__ int lane_groups(int lane) { return lane == 63 ? 9 : 7; }
 
-// Count sources: get4(b0) returns bins b0..b0+3 (b0 % 4 == 0); bins >= 1798 read 0.
+// Count sources: get4(b0) returns bins b0..b0+3 (b0 % 4 == 0); bins >= 1798 read 0.  (The LDS
+// sources also give one bin, get1(b), b < 1798.)
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 // x.lo + x.hi + c (one v_dot2_u32_u16)
 __device__ __forceinline__ uint32_t pair_sum(uint32_t x, uint32_t c) {
@@ -91,10 +92,12 @@ struct SrcLds16 {  // u16-packed row in LDS (cold tile: counts of the new record
     const uint2 w = *reinterpret_cast<const uint2*>(row + (b0 >> 1));
     return pair_sum(w.x, pair_sum(w.y, 0u));
   }
+  __device__ __forceinline__ uint32_t get1(int b) const { return (row[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu; }
 };
 struct SrcLds32 {  // u32 row in LDS, stride ROW, bins 1798/1799 zero
   const uint32_t* row;
   __device__ __forceinline__ uint4 get4(int b0) const { return *reinterpret_cast<const uint4*>(row + b0); }
+  __device__ __forceinline__ uint32_t get1(int b) const { return row[b]; }
 };
 struct SrcRow32 {  // state row, stride ROW = 1800 u32, 16-B aligned
   const uint32_t* row;
@@ -138,7 +141,7 @@ __device__ __forceinline__ uint32_t sum4(uint4 v) { return v.x + v.y + v.z + v.w
 // The lane's nine group sums at a width that cannot wrap.  Four legal buckets (each
 // <= 2^31 - 1 in an int32 row, a u32 in a state row) sum to 2^32 and more, but stay below
 // 2^34: the low words, and bits 32..33 of all nine packed in one register (nine u64 sums
-// took k_accum_cold_h from 125 to 137 VGPRs, past the 128 at which two of its workgroups
+// took k_accum_cold_dense from 125 to 137 VGPRs, past the 128 at which two of its workgroups
 // share a CU; this form compiles to 122).
 // Plain uint32_t[9] sums are for sources whose record count bounds the row: a cold
 // half-tile (<= 65535 records), one chunk of a big one (<= 2^20).

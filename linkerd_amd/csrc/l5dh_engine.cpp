@@ -74,7 +74,7 @@ const void* host_mapped_ptr(const void* p) {
 Plan plan(l5dh_ctx* c) {
   return Plan{c->d_tile_tot, c->d_enc_base, c->d_enc_h0, c->d_enc_dw, c->d_cold_item,
               c->split_item.as<uint2>(), c->d_hot_list, c->d_tile_flags, c->d_header,
-              c->h_header_dev + 5};
+              c->h_header_dev + PIN_BIG};
 }
 
 Segs segs_view(l5dh_ctx* c) {
@@ -187,7 +187,7 @@ int aggregate(l5dh_ctx* c, int final_mode, int reset, Outputs out, bool encode) 
   }
   if (encode) {  // the unpacked encoding's size comes from the plan (one host wait)
     uint32_t words = 0;
-    HIPCHK(c, hipMemcpyAsync(&words, c->d_header + 5 + 4 * ((c->F + 1023) / 1024), 4, hipMemcpyDeviceToHost,
+    HIPCHK(c, hipMemcpyAsync(&words, c->d_header + plan_header(c->F).enc_words(), 4, hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (int r = ensure(c, c->m_unpacked, (size_t)words * 4 + 16)) return r;
@@ -214,7 +214,7 @@ int aggregate(l5dh_ctx* c, int final_mode, int reset, Outputs out, bool encode) 
     // The two streams cost ~20 us of idle GPU (the fork's and the join's barrier packets);
     // they pay only when there are big tiles, so the last plan the host has seen picks the
     // order (a hint: either order is correct; k_plan_b writes it to a mapped host word)
-    const bool big_seen = __atomic_load_n(c->h_header + 5, __ATOMIC_RELAXED) != 0u;
+    const bool big_seen = __atomic_load_n(c->h_header + PIN_BIG, __ATOMIC_RELAXED) != 0u;
     if (split_items && big_seen) {
       HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
       HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -252,10 +252,10 @@ int fold(l5dh_ctx* c) {
 }
 
 // Invalid series ids: k_rbin1 (k_fold1) adds to the device counter d_err (never
-// reset); k_rfix1 (a copy, after k_fold1) puts it into the pinned, mapped h_header[4].  The host value only grows, so comparing it with the number of
+// reset); k_rfix1 (a copy, after k_fold1) puts it into the pinned, mapped h_header[PIN_ERR].  The host value only grows, so comparing it with the number of
 // reports already returned needs no synchronization.
 int check_err(l5dh_ctx* c) {
-  const uint32_t seen = __atomic_load_n(c->h_header + 4, __ATOMIC_ACQUIRE);
+  const uint32_t seen = __atomic_load_n(c->h_header + PIN_ERR, __ATOMIC_ACQUIRE);
   if (seen != c->err_reported) {
     c->err_reported = seen;
     return fail(c, -EINVAL, "series id >= max_series in an ingest batch (those samples were dropped)");
@@ -293,7 +293,7 @@ int do_ingest(l5dh_ctx* c, const uint32_t* series, const float* values, size_t n
         (uint32_t)std::min<size_t>(c->hot_chunk & ~3u, std::max<size_t>(16384, (fill + 1023) & ~(size_t)1023));
     HIPCHK(c, launch_fold1(ds, dv, n, chunk, state(c), tables(c), c->d_err, vec, (c->variant & 1) != 0, c->stream));
     c->fold_last = n;
-    HIPCHK(c, hipMemcpyAsync(c->h_header + 4, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_header + PIN_ERR, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
     return 0;
   }
   auto& sg = c->segs[c->nseg];
@@ -329,7 +329,7 @@ int do_ingest(l5dh_ctx* c, const uint32_t* series, const float* values, size_t n
   a.tb = tables(c);
   a.sumfix = c->d_sumfix;
   a.err = c->d_err;
-  a.err_host = c->h_header_dev + 4;
+  a.err_host = c->h_header_dev + PIN_ERR;
   a.kest = c->d_kest;
   a.kprev = c->d_kprev;
   a.meta = sg.meta;
@@ -361,7 +361,7 @@ int do_ingest(l5dh_ctx* c, const uint32_t* series, const float* values, size_t n
   }
   sg.n = n;
   c->nseg++;
-  return 0;  // (k_rfix1 wrote the invalid-id count to h_header[4])
+  return 0;  // (k_rfix1 wrote the invalid-id count to h_header[PIN_ERR])
 }
 
 // Wait until the caller's buffers of this call have been read by the device.
@@ -777,7 +777,7 @@ int l5dh_open(l5dh_ctx** out, uint32_t max_series, uint32_t device_mask) {
             c->d_lut.alloc(LUT_N * 4) && c->d_lut2.alloc(LUT2_N * 16) && c->d_counts.alloc(S * ROW * 4) &&
             c->d_total.alloc(S * 8) && c->d_sumfix.alloc(S * 8) && c->d_dirty.alloc(F) && c->d_err.alloc(4) &&
             c->d_tile_tot.alloc(F * 4) && c->d_cold_item.alloc((F + 1) * 16) && c->d_hot_list.alloc(F * 4) &&
-            c->d_header.alloc(plan_header_words((uint32_t)F) * 4) && c->d_tile_flags.alloc(F) &&
+            c->d_header.alloc(plan_header((uint32_t)F).words() * 4) && c->d_tile_flags.alloc(F) &&
             c->d_enc_base.alloc(F * 4) && c->d_enc_h0.alloc(F * 4) && c->d_enc_dw.alloc(2 * F * 4) &&
             c->d_kest.alloc(2 * F * 4) && c->d_kprev.alloc(2 * F * 4);
   const size_t meta_bytes = (size_t)meta_layout((uint32_t)F).words() * 4;
@@ -787,8 +787,8 @@ int l5dh_open(l5dh_ctx** out, uint32_t max_series, uint32_t device_mask) {
     (void)hipGetLastError();
     return bail(-ENOMEM);
   }
-  if (hipHostMalloc((void**)&c->h_header, 32, hipHostMallocMapped) != hipSuccess) return bail(-ENOMEM);  // [4]: err count
-  memset(c->h_header, 0, 32);
+  if (hipHostMalloc((void**)&c->h_header, PIN_WORDS * 4, hipHostMallocMapped) != hipSuccess) return bail(-ENOMEM);
+  memset(c->h_header, 0, PIN_WORDS * 4);
   if (hipHostGetDevicePointer((void**)&c->h_header_dev, c->h_header, 0) != hipSuccess) return bail(-ENOMEM);
   // constant tables (built on the host once per process: l5dh_tables.cpp)
   const HostTables* ht = nullptr;

@@ -28,17 +28,6 @@ constexpr int MAX_SEG = 8;
 constexpr int WG = 1024;            // threads per workgroup of the heavy kernels
 constexpr uint32_t COLD_LIMIT_MAX = 65535u;  // u16 LDS bins cannot overflow below this
 
-// LDS bytes of the accumulate kernels: 16 u16-packed rows + the half-tile's sumfix + the
-// bucket midpoints (cold half-tiles), 16 u32 rows (big half-tiles)
-constexpr size_t ACC_COLDH_LDS = (size_t)16 * CROW * 4 + 16 * 8 + ROW * 4;  // half-tile cold items
-constexpr int ENC_LIST = 256;  // (sparse export) first-touched buckets listed per row of a half-tile item
-constexpr size_t ACC_COLDHE_LDS = ACC_COLDH_LDS + 2 * 16 * 4 + (size_t)16 * ENC_LIST * 2;
-constexpr size_t ACC_SPLIT_LDS = (size_t)16 * HROW * 4;
-// k_fold1 (samples, not records): u32 rows of 16 series or u16-packed rows of 32, lane-private
-// u64 value sums, the bucket LUT
-constexpr size_t FOLD16_LDS = (size_t)16 * HROW * 4 + 16 * 64 * 8 + 1024 * 8;
-constexpr size_t FOLD32_LDS = (size_t)TILE * CROW * 4 + TILE * 64 * 8 + 1024 * 8;
-
 struct Tables {            // constant tables in HBM (a few KB each, L2 resident)
   const int32_t* lim_pad;  // [2048] limits padded with Int.MaxValue
   const int32_t* mid;      // [1798] value reported for bucket b
@@ -128,13 +117,30 @@ struct Plan {
   uint2* split_item;       // [split items] {tile | half << 15, chunk} of big tiles
   uint32_t* hot_list;      // [F] big tiles
   uint8_t* tile_flags;     // [F] TF_*
-  uint32_t* header;        // [4] cold items, big tiles, cold-item counter, split items; [4 + k B + b] per-workgroup
-                           // sums of quantity k (B = ceil(F / 1024) plan workgroups); [4 + 4 B] split-item
-                           // counter; [5 + 4 B] the unpacked encoding's words (sparse export)
-  uint32_t* big_hint;      // pinned, host-mapped word: this plan's big tiles (the host reads the last value
-                           // it sees only to pick the accumulate's launch order)
+  uint32_t* header;        // [PlanHeader::words()] counts, counters and per-workgroup sums (PlanHeader below)
+  uint32_t* big_hint;      // the pinned header's PIN_BIG word: this plan's big tiles (the host reads the last
+                           // value it sees only to pick the accumulate's launch order)
 };
-__host__ __device__ constexpr uint32_t plan_header_words(uint32_t F) { return 6 + 4 * ((F + 1023) / 1024); }
+// Plan::header (u32 words) of a series space of F tiles; B = ceil(F / 1024) plan workgroups.
+struct PlanHeader {
+  uint32_t B;
+  __host__ __device__ constexpr uint32_t cold_items() const { return 0; }
+  __host__ __device__ constexpr uint32_t big_tiles() const { return 1; }
+  __host__ __device__ constexpr uint32_t cold_ctr() const { return 2; }     // the cold kernel's item counter
+  __host__ __device__ constexpr uint32_t split_items() const { return 3; }
+  // [4][B] workgroup b's sum of quantity k: cold items, big tiles, split items, encoding words
+  __host__ __device__ constexpr uint32_t wg_sum(uint32_t k, uint32_t b) const { return 4 + k * B + b; }
+  __host__ __device__ constexpr uint32_t split_ctr() const { return 4 + 4 * B; }  // k_accum_split's item counter
+  __host__ __device__ constexpr uint32_t enc_words() const { return 5 + 4 * B; }  // the unpacked encoding's words (sparse export)
+  __host__ __device__ constexpr uint32_t words() const { return 6 + 4 * B; }
+};
+__host__ __device__ constexpr PlanHeader plan_header(uint32_t F) { return PlanHeader{(F + 1023) / 1024}; }
+// The pinned, host-mapped header (l5dh_ctx::h_header): words the device writes and the host polls
+enum : uint32_t {
+  PIN_ERR = 4,    // invalid-id count (IngestArgs::err_host; monotonic)
+  PIN_BIG = 5,    // big tiles of the last plan (Plan::big_hint)
+  PIN_WORDS = 8
+};
 // Sparse export (the fleet merge's reduce-scatter): words a tile's rows may take in the
 // unpacked encoding (a row: one word per non-empty bucket, a second one per count >=
 // MERGE_CMAX) -- a clean cold tile at most its records (<= 65535 per tile: no escaped
@@ -171,7 +177,7 @@ struct IngestArgs {
   Tables tb;
   int64_t* sumfix;
   uint32_t* err;           // invalid-id counter (monotonic)
-  uint32_t* err_host;      // mapped pinned word: the counter, copied after level 1
+  uint32_t* err_host;      // the pinned header's PIN_ERR word: the counter, copied after level 1
   uint32_t* kest;          // [K] sampled ids per key (zero between batches)
   uint32_t* kprev;         // [K] exact records per key of the previous batch
   uint32_t* meta;          // the segment's metadata

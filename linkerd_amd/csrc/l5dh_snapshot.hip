@@ -3,9 +3,9 @@
 //
 //   k_plan_a/b     per tile: records over pending segments, cold/big, work items
 //   k_hot_init     zero the rows big tiles accumulate into
-//   k_accum_cold_h cold half-tile: 16 series in u16-packed LDS bins, fused summary +
-//                  dense flush, or the sparse export's encoding (persistent, two
-//                  workgroups per CU)
+//   k_accum_cold_dense / _sparse  cold half-tile: 16 series in u16-packed LDS bins, fused
+//                  summary + dense flush, or the sparse export's encoding (persistent,
+//                  two workgroups per CU)
 //   k_accum_split  big half-tile: (half, chunk) partial in u32 LDS bins, flushed
 //                  with global atomics (persistent)
 //   k_hot_finish   summaries of big tiles from their merged rows
@@ -14,6 +14,8 @@
 //
 // Every (tile, half) key of a segment is one contiguous range of rec16 records
 // (l5dh_kernels.hpp: series in tile | bucket; their value sums are in sumfix).
+#include <type_traits>
+
 #include "l5dh_device.hpp"
 
 namespace l5dh {
@@ -38,7 +40,7 @@ __device__ __forceinline__ uint32_t seg_key_count(const Segs& sg, int j, uint32_
 // k_plan_a / k_plan_b (ceil(F / 1024) workgroups each): k_plan_a classifies tile
 // t = 1024 b + thread (cold: <= cold_limit records; else big, accumulated per half
 // in chunks of hot_chunk records) and stores its workgroup's item counts in
-// header[4 + k B + b]; k_plan_b scans those and writes the lists in tile order.
+// header[wg_sum(k, b)] (PlanHeader); k_plan_b scans those and writes the lists in tile order.
 struct PlanCls {
   uint32_t ci, hot, si, h0, ec;  // ec: the tile's words in the unpacked encoding (sparse export)
 };
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_plan_a(Segs segs, uint32_t F, int fina
   if (threadIdx.x < 4) {
     uint32_t x = 0;
     for (int q = 0; q < 16; ++q) x += red[threadIdx.x][q];
-    plan.header[4 + threadIdx.x * gridDim.x + blockIdx.x] = x;
+    plan.header[PlanHeader{gridDim.x}.wg_sum(threadIdx.x, blockIdx.x)] = x;
   }
 }
 
@@ -111,24 +113,25 @@ __global__ __launch_bounds__(1024) void k_plan_b(Segs segs, uint32_t F, int fina
   __shared__ uint4 big[64];  // {tile, first item, half-0 records, records}
   if (threadIdx.x == 0) nbig = 0;  // (visible after the scans' barriers)
   const uint32_t B = gridDim.x;
+  const PlanHeader H{B};
   {
     uint32_t x[4], tx[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = threadIdx.x < blockIdx.x ? plan.header[4 + k * B + threadIdx.x] : 0u;
+    for (int k = 0; k < 4; ++k) x[k] = threadIdx.x < blockIdx.x ? plan.header[H.wg_sum(k, threadIdx.x)] : 0u;
     block_excl_scan4<1024>(x, lds4, tx);
     if (threadIdx.x < 4) base[threadIdx.x] = tx[threadIdx.x];
     if (blockIdx.x == 0) {
       uint32_t y[4], ty[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = threadIdx.x < B ? plan.header[4 + k * B + threadIdx.x] : 0u;
+      for (int k = 0; k < 4; ++k) y[k] = threadIdx.x < B ? plan.header[H.wg_sum(k, threadIdx.x)] : 0u;
       block_excl_scan4<1024>(y, lds4, ty);
-      if (threadIdx.x == 0) {  // header: cold items, big tiles, cold-item counter, split items
-        plan.header[0] = ty[0];
-        plan.header[1] = ty[1];
-        plan.header[2] = 0u;
-        plan.header[3] = ty[2];
-        plan.header[4 + 4 * B] = 0u;   // split-item counter
-        plan.header[5 + 4 * B] = ty[3];  // the unpacked encoding's words
+      if (threadIdx.x == 0) {
+        plan.header[H.cold_items()] = ty[0];
+        plan.header[H.big_tiles()] = ty[1];
+        plan.header[H.cold_ctr()] = 0u;
+        plan.header[H.split_items()] = ty[2];
+        plan.header[H.split_ctr()] = 0u;
+        plan.header[H.enc_words()] = ty[3];
         if (plan.big_hint) *reinterpret_cast<volatile uint32_t*>(plan.big_hint) = ty[1];
       }
     }
@@ -213,9 +216,9 @@ __device__ __forceinline__ BigRows big_rows(const State& st, const Outputs& out,
 }
 
 // k_hot_init: big tiles accumulate with global atomics, so clean ones start from
-// zero.  Persistent (the number of big tiles, header[1], is read on the device).
+// zero.  Persistent (the number of big tiles is read from the plan header on the device).
 __global__ __launch_bounds__(256) void k_hot_init(Plan plan, State st, Outputs out, int direct_out) {
-  const uint32_t nh = plan.header[1];
+  const uint32_t nh = plan.header[plan_header(st.F).big_tiles()];
   for (uint32_t i = blockIdx.x; i < nh; i += gridDim.x) {
     const uint32_t t = plan.hot_list[i];
     if (plan.tile_flags[t] & (TF_DIRTY | TF_SOLO)) continue;
@@ -369,15 +372,117 @@ __device__ __forceinline__ void count_tile(const Segs& sg, uint32_t F, uint32_t 
 }
 
 
-// k_accum_cold_h: the cold tiles as half-tile items -- 16 series in one u16-packed LDS
-// histogram (57.6 KB), 512-thread workgroups, two per CU, so one workgroup counts
-// while the other emits its rows (round 4: -0.12 ms of accumulate against one whole
-// tile per 1024-thread workgroup, which held one tile in flight per CU).
-// Item i is half i & 1 of cold item i >> 1.  ENCODE: the fleet merge's sparse export
-// (row encodings, no rows or summaries); half 1's rows start past half 0's room in
-// the tile's encoding range (h0 + 16 words for a clean tile: a row's words never
-// exceed its records; Plan::enc_h0 for a dirty one).
-#ifdef L5DH_PHASES  // development: per-workgroup phase times of k_accum_cold_h
+// ---- the dynamic LDS of the snapshot kernels ----
+// One layout per kernel: byte offsets in layout order (each array's size is in the next
+// line's sum), typed views, and `bytes` -- the one size the function attributes, the
+// launches and the kernels' clears take.
+constexpr size_t LDS_WG = 160 * 1024;  // one workgroup's LDS, which is one CU's
+template <typename T>
+__device__ __forceinline__ T* lds_at(uint32_t* smem, size_t o) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(smem) + o);
+}
+constexpr int HSER = 16;       // series of a half-tile item
+constexpr int COLD_NT = 512;   // threads of a cold workgroup
+constexpr int ENC_LIST = 256;  // (sparse export) first-touched buckets listed per row of a half-tile item
+
+// The cold kernels: the half-tile's bins, its series' sumfix, the bucket midpoints; SPARSE
+// adds, per row, the buckets in the order they were first touched (ColdAddFirstTouch).
+template <bool SPARSE>
+struct ColdLds {
+  static constexpr size_t o_hist = 0;                             // u32 [HSER][CROW] u16 pairs
+  static constexpr size_t o_fixl = o_hist + HSER * CROW * 4;      // i64 [HSER] sumfix of the item's series
+  static constexpr size_t o_midl = o_fixl + HSER * 8;             // i32 [ROW] bucket midpoints ([NB] used)
+  static constexpr size_t o_tcnt = o_midl + ROW * 4;              // u32 [2][HSER] first touches per row, by item parity
+  static constexpr size_t o_tlist = o_tcnt + 2 * HSER * 4;        // u16 [HSER][ENC_LIST] the first ENC_LIST of them
+  static constexpr size_t bytes = SPARSE ? o_tlist + HSER * ENC_LIST * 2 : o_tcnt;
+  // the kernel's static __shared__: rwl[HSER] (sparse), s_next[2] (dense)
+  static constexpr size_t static_bytes = SPARSE ? HSER * 4 : 2 * 4;
+
+  static __device__ __forceinline__ uint32_t* hist(uint32_t* smem) { return lds_at<uint32_t>(smem, o_hist); }
+  static __device__ __forceinline__ int64_t* fixl(uint32_t* smem) { return lds_at<int64_t>(smem, o_fixl); }
+  static __device__ __forceinline__ int32_t* midl(uint32_t* smem) { return lds_at<int32_t>(smem, o_midl); }
+  static __device__ __forceinline__ uint32_t* tcnt(uint32_t* smem) {
+    static_assert(SPARSE, "the sparse tail");
+    return lds_at<uint32_t>(smem, o_tcnt);
+  }
+  static __device__ __forceinline__ uint16_t* tlist(uint32_t* smem) {
+    static_assert(SPARSE, "the sparse tail");
+    return lds_at<uint16_t>(smem, o_tlist);
+  }
+};
+// k_accum_split: u32 bins of a big half-tile's 16 series.
+struct SplitLds {
+  static constexpr size_t o_hist = 0;  // u32 [HSER][HROW]
+  static constexpr size_t bytes = o_hist + HSER * HROW * 4;
+  static __device__ __forceinline__ uint32_t* hist(uint32_t* smem) { return lds_at<uint32_t>(smem, o_hist); }
+};
+// k_fold1 (samples, not records): u32 rows of 16 series (W32) or u16-packed rows of 32,
+// lane-private u64 value sums, the bucket LUT.  hist and vsl are cleared per item.
+template <bool W32>
+struct Fold1Lds {
+  static constexpr int NSER = W32 ? 16 : TILE;
+  static constexpr int RW = W32 ? HROW : CROW;  // LDS words per series row
+  using Row = typename std::conditional<W32, SrcLds32, SrcLds16>::type;
+  static constexpr size_t o_hist = 0;                           // u32 [NSER][RW] u32 / u16 pairs
+  static constexpr size_t o_vsl = o_hist + NSER * RW * 4;       // u64 [NSER][64]
+  static constexpr size_t o_lut2 = o_vsl + NSER * 64 * 8;       // uint2 [LUT2_N]
+  static constexpr size_t bytes = o_lut2 + LUT2_N * 8;
+  static constexpr size_t clear_bytes = o_lut2;
+  static __device__ __forceinline__ uint32_t* hist(uint32_t* smem) { return lds_at<uint32_t>(smem, o_hist); }
+  static __device__ __forceinline__ unsigned long long* vsl(uint32_t* smem) {
+    return lds_at<unsigned long long>(smem, o_vsl);
+  }
+  static __device__ __forceinline__ uint2* lut2(uint32_t* smem) { return lds_at<uint2>(smem, o_lut2); }
+};
+static_assert(ColdLds<false>::bytes == 64928 && ColdLds<true>::bytes == 73248 && SplitLds::bytes == 115200 &&
+                  Fold1Lds<true>::bytes == 131584 && Fold1Lds<false>::bytes == 139776,
+              "the layouts' sizes as they were when written as sums of literals");
+static_assert(ColdLds<true>::bytes <= LDS_WG && SplitLds::bytes <= LDS_WG && Fold1Lds<true>::bytes <= LDS_WG &&
+                  Fold1Lds<false>::bytes <= LDS_WG,
+              "one workgroup's LDS");
+static_assert(2 * (ColdLds<false>::bytes + (ColdLds<false>::static_bytes + 15) / 16 * 16) <= LDS_WG &&
+                  2 * (ColdLds<true>::bytes + (ColdLds<true>::static_bytes + 15) / 16 * 16) <= LDS_WG,
+              "two cold workgroups per CU (static LDS in 16-B units): one counts while the other emits");
+static_assert(ColdLds<true>::o_hist % 16 == 0 && (HSER * CROW * 4) % 16 == 0 && (CROW * 4) % 16 == 0 &&
+                  ColdLds<true>::o_fixl % 8 == 0,
+              "hist is cleared as uint4, whole and row by row; fixl is int64");
+static_assert(SplitLds::o_hist % 16 == 0 && SplitLds::bytes % 16 == 0 && (HROW * 4) % 16 == 0,
+              "hist is cleared and its rows are read (SrcLds32) as uint4");
+static_assert(Fold1Lds<true>::clear_bytes % 16 == 0 && Fold1Lds<false>::clear_bytes % 16 == 0 &&
+                  Fold1Lds<true>::o_vsl % 8 == 0 && Fold1Lds<false>::o_vsl % 8 == 0 && Fold1Lds<true>::o_lut2 % 8 == 0 &&
+                  Fold1Lds<false>::o_lut2 % 8 == 0,
+              "hist and vsl are cleared as uint4; vsl is u64, lut2 uint2");
+
+// ---- two idioms of the kernels below (one wave each) ----
+// An LDS row's nonzero bins added to a global row: 64 consecutive bins per wave atomic.
+template <class Src>
+__device__ __forceinline__ void flush_row_atomic(const Src& src, uint32_t* __restrict__ grow) {
+  const int lane = lane_id();
+  for (int b0 = 0; b0 < NB; b0 += 64) {
+    const int b = b0 + lane;
+    const uint32_t v = b < NB ? src.get1(b) : 0u;
+    if (__ballot(v != 0u)) {
+      if (v) atomicAdd(&grow[b], v);
+    }
+  }
+}
+// A u16-packed LDS row cleared for the next item.
+__device__ __forceinline__ void clear_row(uint32_t* row) {
+  uint4* hr = reinterpret_cast<uint4*>(row);
+  for (int i = lane_id(); i < CROW / 4; i += 64) hr[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// ---- the cold tiles as half-tile items ----
+// 16 series in one u16-packed LDS histogram (57.6 KB), 512-thread workgroups, two per CU,
+// so one workgroup counts while the other emits its rows (round 4: -0.12 ms of accumulate
+// against one whole tile per 1024-thread workgroup, which held one tile in flight per CU).
+// Item i is half i & 1 of cold item i >> 1.  Two kernels over the phases below:
+//   k_accum_cold_dense   rows, totals and summaries of a snapshot, or a fold into the state
+//   k_accum_cold_sparse  the fleet merge's sparse export: row encodings, no rows or summaries
+// The phases take values (pointers into LDS, the item's fields), not references to the
+// kernels' locals (l5dh_ingest.hip's note on how a phase is cut); the kernels keep the
+// barriers, the phase marks and the item order, which is where they differ.
+#ifdef L5DH_PHASES  // development: per-workgroup phase times of the cold kernels
 __device__ unsigned long long g_phase2[1024 * 8];
 #define PH_INIT unsigned long long ph_acc[4] = {0, 0, 0, 0}, ph_t = wall_clock64();
 #define PH_MARK(k)                                 \
@@ -396,291 +501,392 @@ __device__ unsigned long long g_phase2[1024 * 8];
 #define PH_MARK(k)
 #define PH_FLUSH
 #endif
-constexpr int HSER = 16;
-template <bool ENCODE>
-__global__ __launch_bounds__(512, 2) void k_accum_cold_h(Segs segs, Plan plan, State st, Tables tb, Outputs out,
-                                                         uint32_t cold_arg, int final_mode, int reset) {
-  constexpr int NT = 512;
-  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t cold_tiles = cold_arg != DEV_COUNT ? cold_arg : plan.header[0];
-  const uint32_t nitems = 2u * cold_tiles;
-  uint32_t* hist = smem;                                             // [16][900] u16 pairs
-  int64_t* fixl = reinterpret_cast<int64_t*>(smem + HSER * CROW);    // [16] sumfix of the item's series
-  int32_t* midl = reinterpret_cast<int32_t*>(fixl + HSER);           // [NB] bucket midpoints
+
+// An item as it is prefetched, one item ahead: its entry's fields, its sumfix and (one
+// pending segment) each thread's first 16-B group.
+struct ColdItem {
+  uint32_t t, half;
+  bool dirty;         // the tile held live counts
+  uint32_t a, n;      // the half's records in segment 0: first, count
+  uint32_t h0;        // (sparse export) half 0's records in segment 0: the whole count with one segment
+  uint32_t enc_base;  // (sparse export) the tile's first word in the unpacked encoding
+  int64_t fraw;       // sumfix of the half's series (thread & 15), read past S clamped: take_sumfix masks it
+  uint4 x0;           // (one segment) the thread's first group of records
+};
+// Issue the item's loads.  The entry arrives in VGPRs and is pinned there; its fields are
+// workgroup-uniform (readfirstlane), so the range and the tile live in SGPRs.
+template <bool SPARSE>
+__device__ __forceinline__ ColdItem cold_fetch(uint4 ci, uint32_t half, bool one, const uint16_t* b16, const State& st,
+                                               const Plan& plan) {
+  asm volatile("" : "+v"(ci.x), "+v"(ci.y), "+v"(ci.z), "+v"(ci.w));
+  const uint32_t cx = __builtin_amdgcn_readfirstlane(ci.x), cw = __builtin_amdgcn_readfirstlane(ci.w);
+  ColdItem it;
+  it.t = cx & 0x7FFFu;
+  it.half = half;
+  it.dirty = (cx & CI_DIRTY) != 0u;
+  it.a = __builtin_amdgcn_readfirstlane(half ? ci.z : ci.y);
+  it.n = half ? cw >> 16 : cw & 0xFFFFu;
+  it.h0 = cw & 0xFFFFu;
+  it.x0 = make_uint4(0u, 0u, 0u, 0u);
+  if (one) {
+    const uint32_t g = threadIdx.x;
+    it.x0 = *reinterpret_cast<const uint4*>(b16 + (8 * g < it.n ? it.a + 8 * g : it.a));
+  }
+  it.fraw = st.sumfix[min(it.t * TILE + HSER * half + (threadIdx.x & (HSER - 1)), st.S - 1)];
+  it.enc_base = SPARSE ? plan.enc_base[it.t] : 0u;
+  return it;
+}
+
+// The bins, sumfix and midpoints at the kernel's start.
+template <class L>
+__device__ __forceinline__ void cold_lds_init(uint32_t* smem, const int32_t* __restrict__ mid) {
+  uint4* p = reinterpret_cast<uint4*>(L::hist(smem));
+  for (int i = threadIdx.x; i < HSER * CROW / 4; i += COLD_NT) p[i] = make_uint4(0, 0, 0, 0);
+  int32_t* midl = L::midl(smem);
+  for (int i = threadIdx.x; i < NB; i += COLD_NT) midl[i] = mid[i];
+}
+
+// The item's sumfix into LDS (fixl), cleared in the state where it was not zero.
+__device__ __forceinline__ void take_sumfix(const ColdItem& it, int64_t* fixl, const State& st) {
+  if (threadIdx.x < HSER) {
+    const uint32_t s = it.t * TILE + HSER * it.half + threadIdx.x;
+    const int64_t f = s < st.S ? it.fraw : 0;
+    fixl[threadIdx.x] = f;
+    if (f) st.sumfix[s] = 0;
+  }
+}
+
+// One record into the item's bins.
+struct ColdAdd {
+  uint32_t* hist;
+  __device__ __forceinline__ void operator()(uint32_t loc, uint32_t b) const {
+    atomicAdd(&hist[(loc & (HSER - 1)) * CROW + (b >> 1)], (b & 1u) ? 0x10000u : 1u);
+  }
+};
+// (sparse export, clean item) ... and, per row, the buckets in the order they were first
+// touched: the returning add tells a first touch; tcnt[row] counts them (= the row's words:
+// a cold row's counts stay below the escape), the first ENC_LIST are listed.
+// (batching the 8 adds of a group and listing the first touches after them measured
+// +0.02 ms per C4 rank, round 5)
+struct ColdAddFirstTouch {
+  uint32_t* hist;
+  uint32_t* tcnt;   // [HSER] of this item's parity
+  uint16_t* tlist;
+  __device__ __forceinline__ void operator()(uint32_t loc, uint32_t b) const {
+    const uint32_t l = loc & (HSER - 1);
+    const uint32_t old = atomicAdd(&hist[l * CROW + (b >> 1)], (b & 1u) ? 0x10000u : 1u);
+    if ((((b & 1u) ? old >> 16 : old) & 0xFFFFu) == 0u) {
+      const uint32_t k = atomicAdd(&tcnt[l], 1u);
+      if (k < (uint32_t)ENC_LIST) tlist[l * ENC_LIST + k] = (uint16_t)b;
+    }
+  }
+};
+
+// The count of one item.  One pending segment: the thread's first group came with the item,
+// and the next one is loaded while this one is counted.  More: segment by segment.
+template <class Add>
+__device__ __forceinline__ void count_item_prefetched(const uint16_t* b16, uint32_t a, uint32_t n, uint4 x0, Add add) {
+  const uint32_t g0 = (n + 7) / 8;
+  const uint4* p0 = reinterpret_cast<const uint4*>(b16 + a);
+  uint4 x = x0;
+  for (uint32_t g = threadIdx.x; g < g0; g += COLD_NT) {
+    const uint4 cx = x;
+    const uint32_t gn = g + COLD_NT;
+    x = gn < g0 ? p0[gn] : make_uint4(0u, 0u, 0u, 0u);
+    count16(cx, min(8u, n - 8 * g), add);
+  }
+}
+template <class Add>
+__device__ __forceinline__ void count_item_segments(const Segs& segs, uint32_t F, uint32_t t, uint32_t half, Add add) {
+  for (int j = 0; j < segs.n; ++j) {
+    const KeyRange r = seg_key(segs, j, F, t, half);
+    const uint32_t n = r.e - r.a, g0 = (n + 7) / 8;
+    const uint4* p = reinterpret_cast<const uint4*>(r.r16 + r.a);
+    for (uint32_t g = threadIdx.x; g < g0; g += COLD_NT) count16(p[g], min(8u, n - 8 * g), add);
+  }
+}
+template <class Add>
+__device__ __forceinline__ void count_item(const ColdItem& it, bool one, const Segs& segs, uint32_t F, Add add) {
+  if (one)
+    count_item_prefetched(segs.rec16[0], it.a, it.n, it.x0, add);
+  else
+    count_item_segments(segs, F, it.t, it.half, add);
+}
+
+// (sparse export) The half's first word in its tile's encoding range: half 1's rows start
+// past half 0's room (its records + 16 words for a clean tile: a row's words never exceed
+// its records; Plan::enc_h0 for a dirty one).
+__device__ __forceinline__ uint32_t enc_half_base(const ColdItem& it, const Segs& segs, uint32_t F, const Plan& plan) {
+  if (!it.half) return it.enc_base;
+  if (it.dirty) return it.enc_base + plan.enc_h0[it.t];
+  uint32_t h0 = it.h0;
+  for (int j = 1; j < segs.n; ++j) h0 += seg_key_count(segs, j, F, 2 * it.t);
+  return it.enc_base + h0 + HSER;
+}
+
+// (sparse export) A clean item: each row's words = its first touches (tc16); entries in
+// touch order (the decoder adds a source's entries in any order) with the counts from the
+// bins; only the touched bins are cleared.  A row with more than ENC_LIST touches is
+// encoded and cleared from its whole bin row.
+__device__ __forceinline__ void emit_sparse_clean(uint32_t* hist, const uint32_t* tc16, const uint16_t* tlist,
+                                                  const int64_t* fixl, uint32_t s0, uint32_t hb, uint32_t S,
+                                                  const Outputs& out) {
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  for (int loc = w; loc < HSER; loc += COLD_NT / 64) {
+    const uint32_t s = s0 + loc;
+    const uint32_t n = tc16[loc];
+    uint32_t at = hb;
+    for (int l = 0; l < loc; ++l) at += tc16[l];
+    uint32_t* row = hist + loc * CROW;
+    if (s < S) {
+      if (n <= (uint32_t)ENC_LIST) {
+        for (uint32_t i = (uint32_t)lane; i < n; i += 64) {
+          const uint32_t b = tlist[loc * ENC_LIST + i];
+          const uint32_t c = (row[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu;
+          out.enc[at + i] = (b << 21) | c;
+        }
+      } else {
+        row_encode(SrcLds16{row}, out.enc, at);
+      }
+      if (lane == 0) {
+        const uint32_t oi = s - out.first;
+        out.roff[oi] = at;
+        out.words[oi] = n;
+        if (out.totals) out.totals[oi] = fixl[loc];
+      }
+    }
+    if (n <= (uint32_t)ENC_LIST) {  // (a wave's LDS ops stay in order: the reads above come first)
+      for (uint32_t i = (uint32_t)lane; i < n; i += 64) row[tlist[loc * ENC_LIST + i] >> 1] = 0u;
+    } else {
+      clear_row(row);
+    }
+  }
+}
+
+// (sparse export) A dirty item: the rows are the bins + the state rows.  Their words first
+// (rwl; a barrier follows), then their encodings, each row past the ones before it.
+__device__ __forceinline__ void sparse_dirty_words(const uint32_t* hist, uint32_t s0, const State& st, uint32_t* rwl) {
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  for (int loc = w; loc < HSER; loc += COLD_NT / 64) {
+    const uint32_t s = s0 + loc;
+    uint32_t nw = 0;
+    if (s < st.S)
+      nw = row_words(SrcSum2<SrcLds16, SrcRow32>{SrcLds16{hist + loc * CROW}, SrcRow32{st.counts + (size_t)s * ROW}});
+    if (lane == 0) rwl[loc] = nw;
+  }
+}
+__device__ __forceinline__ void emit_sparse_dirty(uint32_t* hist, const uint32_t* rwl, const int64_t* fixl, uint32_t s0,
+                                                  uint32_t hb, const State& st, const Outputs& out) {
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  for (int loc = w; loc < HSER; loc += COLD_NT / 64) {
+    const uint32_t s = s0 + loc;
+    if (s < st.S) {
+      uint32_t at = hb;
+      for (int l = 0; l < loc; ++l) at += rwl[l];
+      row_encode(SrcSum2<SrcLds16, SrcRow32>{SrcLds16{hist + loc * CROW}, SrcRow32{st.counts + (size_t)s * ROW}}, out.enc,
+                 at);
+      if (lane == 0) {
+        const uint32_t oi = s - out.first;
+        out.roff[oi] = at;
+        out.words[oi] = rwl[loc];
+        if (out.totals) out.totals[oi] = fixl[loc] + st.total[s];
+      }
+    }
+    clear_row(hist + loc * CROW);
+  }
+}
+
+// (dense, linear form) A clean, whole half of a resetting snapshot with counts whose 16
+// output rows start 16-B aligned: the summaries here, from the bins; after a barrier the
+// rows leave as one linear stream (store_dense_linear), which also clears the bins.
+// (two series' summaries interleaved per wave, by hand: accumulate +0.02 ms, round 5)
+__device__ __forceinline__ void emit_dense_linear(const uint32_t* hist, const int64_t* fixl, const int32_t* midl,
+                                                  uint32_t s0, uint32_t S, const Outputs& out) {
+  const int w = threadIdx.x >> 6, lane = lane_id();
+  for (int loc = w; loc < HSER; loc += COLD_NT / 64) {
+    const uint32_t s = s0 + loc;
+    // (always a series: the half is whole.  The test stays: without it the wave's two rows are
+    // unrolled and interleaved, 132 VGPRs, and the second workgroup no longer fits the CU)
+    if (s >= S) continue;
+    const uint32_t* row = hist + loc * CROW;
+    const int ng = lane_groups(lane);
+    // 32-bit group sums and the SMALL summary: the row is the item's records, <= 65535
+    uint32_t g[9], nw = 0;
+    if (out.words) {  // (the merge encoding's words: the all-reduce export only)
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        g[q] = 0u;
+        if (q < ng) {
+          const uint4 v = SrcLds16{row}.get4(28 * lane + 4 * q);
+          g[q] = sum4(v);
+          nw += merge_words4(v);
+        }
+      }
+      put_words(nw, out.words + (s - out.first));
+    } else {
+#pragma unroll
+      for (int q = 0; q < 9; ++q) g[q] = q < ng ? SrcLds16{row}.sum4(28 * lane + 4 * q) : 0u;
+    }
+    wave_summary<SrcLds16, true>(g, SrcLds16{row}, fixl[loc], midl, out.summ ? out.summ + (s - out.first) : nullptr);
+    if (lane == 0 && out.totals) out.totals[s - out.first] = fixl[loc];
+  }
+}
+__device__ __forceinline__ void store_dense_linear(uint32_t* hist, int32_t* __restrict__ orows) {
+  uint4* o = reinterpret_cast<uint4*>(orows);
+  constexpr int NCH = HSER * NB / 4;
+  for (int c = threadIdx.x; c < NCH; c += COLD_NT) {
+    const int e0 = 4 * c;
+    const int r0 = e0 / NB, b0 = e0 - r0 * NB;
+    uint32_t* p0 = hist + r0 * CROW + (b0 >> 1);
+    uint32_t* p1 = b0 == NB - 2 ? hist + (r0 + 1) * CROW : p0 + 1;
+    const uint32_t x = *p0, y = *p1;
+    *p0 = 0u;
+    *p1 = 0u;
+    // (nontemporal: the dense rows are the step's output, not read again by it: C3 -0.03 ms;
+    // nontemporal record stores in level 1 took it from 3.3 to 5.7 ms, round 5)
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v4 = {x & 0xFFFFu, x >> 16, y & 0xFFFFu, y >> 16};
+    __builtin_nontemporal_store(v4, reinterpret_cast<u32x4*>(o + c));
+  }
+}
+
+// (dense, row form) Every other item -- a ragged or odd-aligned half, no counts, kept or
+// dirty state, a range, a fold: one emit_series per row, and the row cleared.
+__device__ __forceinline__ void emit_dense_rows(uint32_t* hist, const int64_t* fixl, uint32_t s0, bool dirty, bool keep,
+                                                int final_mode, const State& st, const Tables& tbl, const Outputs& out) {
   const int w = threadIdx.x >> 6;
-  const int lane = lane_id();
+  for (int loc = w; loc < HSER; loc += COLD_NT / 64) {
+    const uint32_t s = s0 + loc;
+    uint32_t* row = hist + loc * CROW;
+    if (s < st.S) emit_series(SrcLds16{row}, s, 0, fixl[loc], dirty, keep, final_mode, st, tbl, out);
+    clear_row(row);
+  }
+}
+
+// Items: blockIdx.x, blockIdx.x + G, then from the plan header's counter (a returning
+// atomic, asked two items ahead through s_next[slot]).  The next item is fetched after the
+// count barrier, so that its loads fly during this item's emission.
+__global__ __launch_bounds__(COLD_NT, 2) void k_accum_cold_dense(Segs segs, Plan plan, State st, Tables tb, Outputs out,
+                                                                 uint32_t cold_arg, int final_mode, int reset) {
+  using L = ColdLds<false>;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  __shared__ uint32_t s_next[2];
+  static_assert(sizeof(s_next) == L::static_bytes, "ColdLds counts the static LDS");
+  const PlanHeader H = plan_header(st.F);
+  const uint32_t cold_tiles = cold_arg != DEV_COUNT ? cold_arg : plan.header[H.cold_items()];
+  const uint32_t nitems = 2u * cold_tiles;
+  uint32_t* const hist = L::hist(smem);
+  int64_t* const fixl = L::fixl(smem);
+  int32_t* const midl = L::midl(smem);
   const bool keep = !(final_mode && reset);
   const uint32_t F = st.F;
   Tables tbl = tb;
   tbl.mid = midl;
-  auto hist_add = [&](uint32_t loc, uint32_t b) {
-    atomicAdd(&hist[(loc & (HSER - 1)) * CROW + (b >> 1)], (b & 1u) ? 0x10000u : 1u);
-  };
-  // (sparse export) per row, the buckets in the order they were first touched: the
-  // returning add tells a first touch; tcnt[par][row] counts them (= the row's words:
-  // a cold row's counts stay below the escape), the first ENC_LIST are listed
-  uint32_t* tcnt = reinterpret_cast<uint32_t*>(midl + ROW);      // [2][HSER] (double-buffered by item parity)
-  uint16_t* tlist = reinterpret_cast<uint16_t*>(tcnt + 2 * HSER);  // [HSER][ENC_LIST]
-  int par = 0;
-  // (batching the 8 adds of a group and listing the first touches after them measured
-  // +0.02 ms per C4 rank, round 5)
-  auto hist_add_enc = [&](uint32_t loc, uint32_t b) {
-    const uint32_t l = loc & (HSER - 1);
-    const uint32_t old = atomicAdd(&hist[l * CROW + (b >> 1)], (b & 1u) ? 0x10000u : 1u);
-    if ((((b & 1u) ? old >> 16 : old) & 0xFFFFu) == 0u) {
-      const uint32_t k = atomicAdd(&tcnt[par * HSER + l], 1u);
-      if (k < (uint32_t)ENC_LIST) tlist[l * ENC_LIST + k] = (uint16_t)b;
-    }
-  };
-  {
-    uint4* p = reinterpret_cast<uint4*>(smem);
-    for (int i = threadIdx.x; i < HSER * CROW / 4; i += NT) p[i] = make_uint4(0, 0, 0, 0);
-    for (int i = threadIdx.x; i < NB; i += NT) midl[i] = tb.mid[i];
-    if (ENCODE && threadIdx.x < 2 * HSER) tcnt[threadIdx.x] = 0u;
-  }
-  // the next item's entry is loaded one item ahead; its sumfix and (one pending
-  // segment) each thread's first 16-B group during this item's emission
+  cold_lds_init<L>(smem, tb.mid);
   const bool one = segs.n == 1;
-  uint32_t t = 0, a = 0, nn = 0, hf = 0, eb = 0, h0e = 0;
-  bool dirty = false;
-  int64_t fraw = 0;
-  uint4 x0 = make_uint4(0u, 0u, 0u, 0u);
   const uint16_t* const b16 = segs.rec16[0];
-  auto fetch = [&](uint4 ci, uint32_t half) {
-    asm volatile("" : "+v"(ci.x), "+v"(ci.y), "+v"(ci.z), "+v"(ci.w));
-    const uint32_t cx = __builtin_amdgcn_readfirstlane(ci.x), cw = __builtin_amdgcn_readfirstlane(ci.w);
-    t = cx & 0x7FFFu;
-    hf = half;
-    dirty = (cx & CI_DIRTY) != 0u;
-    a = __builtin_amdgcn_readfirstlane(half ? ci.z : ci.y);
-    nn = half ? cw >> 16 : cw & 0xFFFFu;
-    h0e = cw & 0xFFFFu;  // (sparse export) half 0's records in segment 0: the whole count with one segment
-    if (one) {
-      const uint32_t g = threadIdx.x;
-      x0 = *reinterpret_cast<const uint4*>(b16 + (8 * g < nn ? a + 8 * g : a));
-    }
-    fraw = st.sumfix[min(t * TILE + HSER * half + (threadIdx.x & (HSER - 1)), st.S - 1)];
-    if (ENCODE) eb = plan.enc_base[t];
-  };
-  __shared__ uint32_t rwl[HSER];  // (sparse export) words of the item's rows
   const uint4* __restrict__ citem = plan.cold_item;
   const uint32_t last = cold_tiles ? cold_tiles - 1u : 0u;
-  // items: blockIdx.x, blockIdx.x + G, then from the counter, asked two items ahead (the
-  // sparse export: blockIdx.x + k G)
-  __shared__ uint32_t s_next[2];
-  uint32_t* const ctr = plan.header + 2;  // zeroed by k_plan_b
+  uint32_t* const ctr = plan.header + H.cold_ctr();  // zeroed by k_plan_b
   const uint32_t G2 = 2u * gridDim.x;
-  if (!ENCODE && threadIdx.x == 0) s_next[0] = G2 + atomicAdd(ctr, 1u);
+  if (threadIdx.x == 0) s_next[0] = G2 + atomicAdd(ctr, 1u);
   uint32_t item = blockIdx.x, item1 = blockIdx.x + gridDim.x;
-  if (item < nitems) fetch(citem[item >> 1], item & 1u);
+  ColdItem nxt{};
+  if (item < nitems) nxt = cold_fetch<false>(citem[item >> 1], item & 1u, one, b16, st, plan);
   uint4 cn = citem[min(item1 >> 1, last)];
   __syncthreads();
   PH_INIT
-  for (; item < nitems; par ^= 1) {
-    const uint32_t tc = t, hc = hf, ebc = eb, h0c = h0e, ac = a, nc = nn;
-    const bool dc = dirty;
-    const uint4 xc = x0;
-    const int64_t fc = fraw;
-    uint32_t item2 = 0, asked = 0;
-    if (ENCODE) {
-      // (sparse items emit little: the next item's entry fields and loads, its successor's
-      // entry and the counter ask go in flight here, ahead of this item's count)
-      // static item order: the counter's returning atomic, waited for inside every short
-      // item, cost the sparse export 0.80 -> 0.56 ms per C4 rank (profiles/r04r_ab.txt)
-      item2 = item1 + gridDim.x;
-      fetch(cn, item1 & 1u);
-      cn = citem[min(item2 >> 1, last)];
-    }
-    if (threadIdx.x < HSER) {
-      const uint32_t s = tc * TILE + HSER * hc + threadIdx.x;
-      const int64_t f = s < st.S ? fc : 0;
-      fixl[threadIdx.x] = f;
-      if (f) st.sumfix[s] = 0;
-    }
-    if (one) {
-      const uint32_t g0 = (nc + 7) / 8;
-      const uint4* p0 = reinterpret_cast<const uint4*>(b16 + ac);
-      uint4 x = xc;
-      for (uint32_t g = threadIdx.x; g < g0; g += NT) {
-        const uint4 cx = x;
-        const uint32_t gn = g + NT;
-        x = gn < g0 ? p0[gn] : make_uint4(0u, 0u, 0u, 0u);
-        if (ENCODE && !dc)
-          count16(cx, min(8u, nc - 8 * g), hist_add_enc);
-        else
-          count16(cx, min(8u, nc - 8 * g), hist_add);
-      }
-    } else {
-      for (int j = 0; j < segs.n; ++j) {
-        const KeyRange r = seg_key(segs, j, F, tc, hc);
-        const uint32_t n = r.e - r.a, g0 = (n + 7) / 8;
-        const uint4* p = reinterpret_cast<const uint4*>(r.r16 + r.a);
-        for (uint32_t g = threadIdx.x; g < g0; g += NT) {
-          if (ENCODE && !dc)
-            count16(p[g], min(8u, n - 8 * g), hist_add_enc);
-          else
-            count16(p[g], min(8u, n - 8 * g), hist_add);
-        }
-      }
-    }
+  for (int slot = 0; item < nitems; slot ^= 1) {
+    const ColdItem cur = nxt;
+    take_sumfix(cur, fixl, st);
+    count_item(cur, one, segs, F, ColdAdd{hist});
     __syncthreads();  // counts complete; fixl visible
     PH_MARK(0)
-    if (ENCODE && threadIdx.x < HSER) tcnt[(par ^ 1) * HSER + threadIdx.x] = 0u;  // the next item's (counted after the end barrier)
-    if (!ENCODE) {
-      fetch(cn, item1 & 1u);  // (past the last item: a harmless refetch)
-      item2 = s_next[par];
-      if (threadIdx.x == 0) asked = G2 + atomicAdd(ctr, 1u);
-      cn = citem[min(item2 >> 1, last)];
-    }
-    const uint32_t s0 = tc * TILE + HSER * hc;
+    nxt = cold_fetch<false>(cn, item1 & 1u, one, b16, st, plan);  // (past the last item: a harmless refetch)
+    const uint32_t item2 = s_next[slot];
+    uint32_t asked = 0;
+    if (threadIdx.x == 0) asked = G2 + atomicAdd(ctr, 1u);
+    cn = citem[min(item2 >> 1, last)];
+    const uint32_t s0 = cur.t * TILE + HSER * cur.half;
     const uint32_t oi0 = s0 - out.first;
-    const bool linear = !keep && !dc && out.counts != nullptr && s0 >= out.first && oi0 + HSER <= out.count &&
+    const bool linear = !keep && !cur.dirty && out.counts != nullptr && s0 >= out.first && oi0 + HSER <= out.count &&
                         s0 + HSER <= st.S && (oi0 & 1u) == 0u;
-    if (ENCODE && !dc) {
-      // a clean item: each row's words = its first touches; entries in touch order (the
-      // decoder adds a source's entries in any order) with the counts from the bins;
-      // only the touched bins are cleared.  A row with more than ENC_LIST touches is
-      // encoded and cleared from its whole bin row.
-      const uint32_t* tc16 = tcnt + par * HSER;
-      uint32_t hb = ebc;
-      if (hc) {
-        uint32_t h0 = h0c;
-        if (!one)
-          for (int j = 1; j < segs.n; ++j) h0 += seg_key_count(segs, j, F, 2 * tc);
-        hb += h0 + HSER;
-      }
-      PH_MARK(3)
-      for (int loc = w; loc < HSER; loc += NT / 64) {
-        const uint32_t s = s0 + loc;
-        const uint32_t n = tc16[loc];
-        uint32_t at = hb;
-        for (int l = 0; l < loc; ++l) at += tc16[l];
-        uint32_t* row = hist + loc * CROW;
-        if (s < st.S) {
-          if (n <= (uint32_t)ENC_LIST) {
-            for (uint32_t i = (uint32_t)lane; i < n; i += 64) {
-              const uint32_t b = tlist[loc * ENC_LIST + i];
-              const uint32_t c = (row[b >> 1] >> ((b & 1u) * 16)) & 0xFFFFu;
-              out.enc[at + i] = (b << 21) | c;
-            }
-          } else {
-            row_encode(SrcLds16{row}, out.enc, at);
-          }
-          if (lane == 0) {
-            const uint32_t oi = s - out.first;
-            out.roff[oi] = at;
-            out.words[oi] = n;
-            if (out.totals) out.totals[oi] = fixl[loc];
-          }
-        }
-        if (n <= (uint32_t)ENC_LIST) {  // (a wave's LDS ops stay in order: the reads above come first)
-          for (uint32_t i = (uint32_t)lane; i < n; i += 64) row[tlist[loc * ENC_LIST + i] >> 1] = 0u;
-        } else {
-          uint4* hr = reinterpret_cast<uint4*>(row);
-          for (int i = lane; i < CROW / 4; i += 64) hr[i] = make_uint4(0u, 0u, 0u, 0u);
-        }
-      }
-      PH_MARK(1)
-    } else if (ENCODE) {
-      for (int loc = w; loc < HSER; loc += NT / 64) {
-        const uint32_t s = s0 + loc;
-        uint32_t nw = 0;
-        if (s < st.S)
-          nw = dc ? row_words(SrcSum2<SrcLds16, SrcRow32>{SrcLds16{hist + loc * CROW}, SrcRow32{st.counts + (size_t)s * ROW}})
-                  : row_words(SrcLds16{hist + loc * CROW});
-        if (lane == 0) rwl[loc] = nw;
-      }
-      uint32_t hb = ebc;  // this half's first word
-      if (hc) {
-        if (dc) {
-          hb += plan.enc_h0[tc];
-        } else {
-          uint32_t h0 = h0c;
-          for (int j = 1; j < segs.n; ++j) h0 += seg_key_count(segs, j, F, 2 * tc);
-          hb += h0 + HSER;
-        }
-      }
-      __syncthreads();  // rwl complete
-      for (int loc = w; loc < HSER; loc += NT / 64) {
-        const uint32_t s = s0 + loc;
-        if (s < st.S) {
-          uint32_t at = hb;
-          for (int l = 0; l < loc; ++l) at += rwl[l];
-          if (dc)
-            row_encode(SrcSum2<SrcLds16, SrcRow32>{SrcLds16{hist + loc * CROW}, SrcRow32{st.counts + (size_t)s * ROW}},
-                       out.enc, at);
-          else
-            row_encode(SrcLds16{hist + loc * CROW}, out.enc, at);
-          if (lane == 0) {
-            const uint32_t oi = s - out.first;
-            out.roff[oi] = at;
-            out.words[oi] = rwl[loc];
-            if (out.totals) out.totals[oi] = fixl[loc] + (dc ? st.total[s] : 0);
-          }
-        }
-        uint4* hr = reinterpret_cast<uint4*>(hist + loc * CROW);  // cleared for the next item
-        for (int i = lane; i < CROW / 4; i += 64) hr[i] = make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-    // (two series' summaries interleaved per wave, unrolled: accumulate +0.02 ms, round 5)
-    for (int loc = w; !ENCODE && loc < HSER; loc += NT / 64) {
-      const uint32_t s = s0 + loc;
-      const uint32_t* row = hist + loc * CROW;
-      if (s < st.S) {
-        if (linear) {
-          const int ng = lane_groups(lane);
-          // 32-bit group sums and the SMALL summary: the row is the item's records, <= 65535
-          uint32_t g[9], nw = 0;
-          if (out.words) {  // (the merge encoding's words: the all-reduce export only)
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-              g[q] = 0u;
-              if (q < ng) {
-                const uint4 v = SrcLds16{row}.get4(28 * lane + 4 * q);
-                g[q] = sum4(v);
-                nw += merge_words4(v);
-              }
-            }
-            put_words(nw, out.words + (s - out.first));
-          } else {
-#pragma unroll
-            for (int q = 0; q < 9; ++q) g[q] = q < ng ? SrcLds16{row}.sum4(28 * lane + 4 * q) : 0u;
-          }
-          wave_summary<SrcLds16, true>(g, SrcLds16{row}, fixl[loc], midl, out.summ ? out.summ + (s - out.first) : nullptr);
-          if (lane == 0 && out.totals) out.totals[s - out.first] = fixl[loc];
-        } else {
-          emit_series(SrcLds16{row}, s, 0, fixl[loc], dc, keep, final_mode, st, tbl, out);
-        }
-      }
-      if (!linear) {
-        uint4* hr = reinterpret_cast<uint4*>(hist + loc * CROW);
-        for (int i = lane; i < CROW / 4; i += 64) hr[i] = make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
     if (linear) {
+      emit_dense_linear(hist, fixl, midl, s0, st.S, out);
       __syncthreads();  // the summaries have read the rows
       PH_MARK(1)
-      uint4* o = reinterpret_cast<uint4*>(out.counts + (size_t)oi0 * NB);
-      constexpr int NCH = HSER * NB / 4;
-      for (int c = threadIdx.x; c < NCH; c += NT) {
-        const int e0 = 4 * c;
-        const int r0 = e0 / NB, b0 = e0 - r0 * NB;
-        uint32_t* p0 = hist + r0 * CROW + (b0 >> 1);
-        uint32_t* p1 = b0 == NB - 2 ? hist + (r0 + 1) * CROW : p0 + 1;
-        const uint32_t x = *p0, y = *p1;
-        *p0 = 0u;
-        *p1 = 0u;
-        // (nontemporal: the dense rows are the step's output, not read again by it: C3 -0.03 ms;
-        // nontemporal record stores in level 1 took it from 3.3 to 5.7 ms, round 5)
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 v4 = {x & 0xFFFFu, x >> 16, y & 0xFFFFu, y >> 16};
-        __builtin_nontemporal_store(v4, reinterpret_cast<u32x4*>(o + c));
-      }
+      store_dense_linear(hist, out.counts + (size_t)oi0 * NB);
+    } else {
+      emit_dense_rows(hist, fixl, s0, cur.dirty, keep, final_mode, st, tbl, out);
     }
     if (threadIdx.x == 0) {
-      st.dirty[tc] = keep ? 1 : 0;
-      if (!ENCODE) s_next[par ^ 1] = asked;
+      st.dirty[cur.t] = keep ? 1 : 0;
+      s_next[slot ^ 1] = asked;
     }
+    __syncthreads();
+    PH_MARK(2)
+    item = item1;
+    item1 = item2;
+  }
+  PH_FLUSH
+}
+
+// Items: blockIdx.x + k G.  A static order: the counter's returning atomic, waited for
+// inside every short item, cost the sparse export 0.80 -> 0.56 ms per C4 rank
+// (profiles/r04r_ab.txt).  Sparse items emit little, so the next item's entry fields and
+// loads and its successor's entry go in flight ahead of this item's count.  The export is
+// a whole-range resetting one (aggregate() checks): every tile it emits ends clean.
+__global__ __launch_bounds__(COLD_NT, 2) void k_accum_cold_sparse(Segs segs, Plan plan, State st, Tables tb, Outputs out,
+                                                                  uint32_t cold_arg) {
+  using L = ColdLds<true>;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  __shared__ uint32_t rwl[HSER];  // words of a dirty item's rows
+  static_assert(sizeof(rwl) == L::static_bytes, "ColdLds counts the static LDS");
+  const uint32_t cold_tiles = cold_arg != DEV_COUNT ? cold_arg : plan.header[plan_header(st.F).cold_items()];
+  const uint32_t nitems = 2u * cold_tiles;
+  uint32_t* const hist = L::hist(smem);
+  int64_t* const fixl = L::fixl(smem);
+  uint32_t* const tcnt = L::tcnt(smem);
+  uint16_t* const tlist = L::tlist(smem);
+  const uint32_t F = st.F;
+  cold_lds_init<L>(smem, tb.mid);
+  if (threadIdx.x < 2 * HSER) tcnt[threadIdx.x] = 0u;
+  const bool one = segs.n == 1;
+  const uint16_t* const b16 = segs.rec16[0];
+  const uint4* __restrict__ citem = plan.cold_item;
+  const uint32_t last = cold_tiles ? cold_tiles - 1u : 0u;
+  uint32_t item = blockIdx.x, item1 = blockIdx.x + gridDim.x;
+  ColdItem nxt{};
+  if (item < nitems) nxt = cold_fetch<true>(citem[item >> 1], item & 1u, one, b16, st, plan);
+  uint4 cn = citem[min(item1 >> 1, last)];
+  __syncthreads();
+  PH_INIT
+  for (int par = 0; item < nitems; par ^= 1) {
+    const ColdItem cur = nxt;
+    const uint32_t item2 = item1 + gridDim.x;
+    nxt = cold_fetch<true>(cn, item1 & 1u, one, b16, st, plan);  // (past the last item: a harmless refetch)
+    cn = citem[min(item2 >> 1, last)];
+    take_sumfix(cur, fixl, st);
+    uint32_t* const tc16 = tcnt + par * HSER;  // this item's first touches per row
+    if (cur.dirty)
+      count_item(cur, one, segs, F, ColdAdd{hist});
+    else
+      count_item(cur, one, segs, F, ColdAddFirstTouch{hist, tc16, tlist});
+    __syncthreads();  // counts complete; fixl visible
+    PH_MARK(0)
+    if (threadIdx.x < HSER) tcnt[(par ^ 1) * HSER + threadIdx.x] = 0u;  // the next item's (counted after the end barrier)
+    const uint32_t s0 = cur.t * TILE + HSER * cur.half;
+    const uint32_t hb = enc_half_base(cur, segs, F, plan);
+    if (!cur.dirty) {
+      PH_MARK(3)
+      emit_sparse_clean(hist, tc16, tlist, fixl, s0, hb, st.S, out);
+      PH_MARK(1)
+    } else {
+      sparse_dirty_words(hist, s0, st, rwl);
+      __syncthreads();  // rwl complete
+      emit_sparse_dirty(hist, rwl, fixl, s0, hb, st, out);
+    }
+    if (threadIdx.x == 0) st.dirty[cur.t] = 0;
     __syncthreads();
     PH_MARK(2)
     item = item1;
@@ -712,12 +918,12 @@ template <bool W32>
 __global__ __launch_bounds__(WG) void k_fold1(const uint32_t* __restrict__ series, const float* __restrict__ values,
                                               size_t n, uint32_t chunk, State st, Tables tb, uint32_t* __restrict__ err,
                                               int vec) {
+  using L = Fold1Lds<W32>;
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  constexpr int NSER = W32 ? 16 : TILE;
-  constexpr int RW = W32 ? HROW : CROW;                                                 // LDS words per series row
-  uint32_t* hist = smem;                                                                // [NSER][RW] u32 / u16 pairs
-  unsigned long long* vsl = reinterpret_cast<unsigned long long*>(smem + NSER * RW);    // [NSER][64]
-  uint2* lut2 = reinterpret_cast<uint2*>(vsl + NSER * 64);                              // [LUT2_N]
+  constexpr int NSER = L::NSER, RW = L::RW;
+  uint32_t* const hist = L::hist(smem);
+  unsigned long long* const vsl = L::vsl(smem);
+  uint2* const lut2 = L::lut2(smem);
   const int lane = lane_id();
   const int w = threadIdx.x >> 6;
   const uint32_t S = st.S;
@@ -750,7 +956,7 @@ __global__ __launch_bounds__(WG) void k_fold1(const uint32_t* __restrict__ serie
   for (size_t item = blockIdx.x; item < nitems; item += gridDim.x) {
     {
       uint4* q = reinterpret_cast<uint4*>(smem);
-      for (int i = threadIdx.x; i < (NSER * RW + NSER * 64 * 2) / 4; i += WG) q[i] = make_uint4(0, 0, 0, 0);
+      for (int i = threadIdx.x; i < (int)(L::clear_bytes / 16); i += WG) q[i] = make_uint4(0, 0, 0, 0);
     }
     __syncthreads();
     const size_t lo = item * chunk, hi = lo + chunk < n ? lo + chunk : n;
@@ -799,15 +1005,7 @@ __global__ __launch_bounds__(WG) void k_fold1(const uint32_t* __restrict__ serie
     for (int loc = w; loc < NSER; loc += WG / 64) {
       if ((uint32_t)loc >= S) continue;
       const uint64_t vsum = wave_sum(vsl[loc * 64 + lane]);
-      uint32_t* grow = st.counts + (size_t)loc * ROW;
-      const uint32_t* hrow = hist + loc * RW;
-      for (int b0 = 0; b0 < NB; b0 += 64) {  // 64 consecutive bins per wave atomic
-        const int b = b0 + lane;
-        const uint32_t v = b >= NB ? 0u : W32 ? hrow[b] : (hrow[b >> 1] >> ((b & 1) * 16)) & 0xFFFFu;
-        if (__ballot(v != 0u)) {
-          if (v) atomicAdd(&grow[b], v);
-        }
-      }
+      flush_row_atomic(typename L::Row{hist + loc * RW}, st.counts + (size_t)loc * ROW);
       if (lane == 0 && vsum) atomicAdd(reinterpret_cast<unsigned long long*>(&st.total[loc]), (unsigned long long)vsum);
     }
     __syncthreads();  // the LDS rows are read: the next item may clear them
@@ -822,21 +1020,22 @@ __global__ __launch_bounds__(WG) void k_fold1(const uint32_t* __restrict__ serie
 __global__ __launch_bounds__(WG) void k_accum_split(Segs segs, Plan plan, State st, Tables tb, Outputs out,
                                                     int direct_out, uint32_t hot_chunk) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  const uint32_t nitems = plan.header[3];  // persistent: items blockIdx.x, + gridDim.x, ...
+  const PlanHeader H = plan_header(st.F);
+  const uint32_t nitems = plan.header[H.split_items()];  // persistent: items blockIdx.x, + gridDim.x, ...
   const uint32_t F = st.F;
   const int lane = lane_id();
   const int w = threadIdx.x >> 6;
-  uint32_t* hist = smem;  // [16][1800]
+  uint32_t* const hist = SplitLds::hist(smem);
   auto hist_add = [&](uint32_t loc, uint32_t b) { atomicAdd(&hist[(loc & 15u) * HROW + b], 1u); };
   // items: blockIdx.x first, then from a counter (G, G + 1, ...) as workgroups finish
   __shared__ uint32_t s_item;
-  uint32_t* const ctr = plan.header + 4 + 4 * ((F + 1023) / 1024);  // zeroed by k_plan_b
+  uint32_t* const ctr = plan.header + H.split_ctr();  // zeroed by k_plan_b
   for (uint32_t item = blockIdx.x; item < nitems; item = s_item) {
     const uint2 it = plan.split_item[item];
     const uint32_t t = it.x & 0x7FFFu, half = (it.x >> 15) & 1u;
     {
       uint4* q = reinterpret_cast<uint4*>(smem);
-      for (int i = threadIdx.x; i < 16 * HROW / 4; i += WG) q[i] = make_uint4(0, 0, 0, 0);
+      for (int i = threadIdx.x; i < (int)(SplitLds::bytes / 16); i += WG) q[i] = make_uint4(0, 0, 0, 0);
     }
     __syncthreads();
     const uint64_t vlo = (uint64_t)it.y * hot_chunk, vhi = vlo + hot_chunk;
@@ -899,15 +1098,7 @@ __global__ __launch_bounds__(WG) void k_accum_split(Segs segs, Plan plan, State 
       if (threadIdx.x == 0 && half == 0) st.dirty[t] = 0;
     } else if (s < st.S) {
       const BigRows br = big_rows(st, out, plan, t, direct_out);
-      uint32_t* grow = br.base + (size_t)(16 * half + w) * br.stride;
-      const uint32_t* hrow = hist + w * HROW;
-      for (int b0 = 0; b0 < NB; b0 += 64) {  // 64 consecutive bins per wave atomic
-        const int b = b0 + lane;
-        const uint32_t v = b < NB ? hrow[b] : 0u;
-        if (__ballot(v != 0u)) {
-          if (v) atomicAdd(&grow[b], v);
-        }
-      }
+      flush_row_atomic(SrcLds32{hist + w * HROW}, br.base + (size_t)(16 * half + w) * br.stride);
     }
     if (threadIdx.x == 0) s_item = gridDim.x + atomicAdd(ctr, 1u);
     __syncthreads();  // the LDS rows are read: the next item may clear them; the next index visible
@@ -918,7 +1109,7 @@ __global__ __launch_bounds__(WG) void k_accum_split(Segs segs, Plan plan, State 
 // write outputs, update state/dirty.
 __global__ __launch_bounds__(WG) void k_hot_finish(Plan plan, State st, Tables tb, Outputs out, int final_mode,
                                                    int reset, int direct_out) {
-  const uint32_t nv = 2 * plan.header[1];  // persistent: (big tile, half) pairs
+  const uint32_t nv = 2 * plan.header[plan_header(st.F).big_tiles()];  // persistent: (big tile, half) pairs
   __shared__ uint32_t rw16[16];  // (sparse export) words of the half's rows
   for (uint32_t vb = blockIdx.x; vb < nv; vb += gridDim.x) {
     const uint32_t t = plan.hot_list[vb >> 1];
@@ -1053,17 +1244,19 @@ extern "C" __attribute__((visibility("default"))) int l5dh_dev_phases2(unsigned 
 
 hipError_t set_snapshot_attributes() {
   hipError_t e = hipSuccess;
-  e = hipFuncSetAttribute((const void*)k_accum_cold_h<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)ACC_COLDH_LDS);
+  e = hipFuncSetAttribute((const void*)k_accum_cold_dense, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)ColdLds<false>::bytes);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)k_accum_cold_h<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)ACC_COLDHE_LDS);
+  e = hipFuncSetAttribute((const void*)k_accum_cold_sparse, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)ColdLds<true>::bytes);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)k_accum_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ACC_SPLIT_LDS);
+  e = hipFuncSetAttribute((const void*)k_accum_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SplitLds::bytes);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)k_fold1<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLD16_LDS);
+  e = hipFuncSetAttribute((const void*)k_fold1<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)Fold1Lds<true>::bytes);
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)k_fold1<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FOLD32_LDS);
+  return hipFuncSetAttribute((const void*)k_fold1<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)Fold1Lds<false>::bytes);
 }
 
 // Sparse export: the words of each half of a dirty tile's state rows (one wave per
@@ -1093,7 +1286,7 @@ hipError_t launch_enc_dirty(State st, Plan plan, hipStream_t s) {
 
 hipError_t launch_plan(Segs segs, uint32_t F, int final_mode, uint32_t cold_limit, uint32_t hot_chunk,
                        const uint8_t* dirty, int direct_out, int encode, Plan plan, hipStream_t st) {
-  const uint32_t B = (F + 1023) / 1024;  // header holds plan_header_words(F) words
+  const uint32_t B = plan_header(F).B;  // one workgroup per 1024 tiles
   hipLaunchKernelGGL(k_plan_a, dim3(B), dim3(1024), 0, st, segs, F, final_mode, cold_limit, hot_chunk, dirty, encode,
                      plan);
   hipLaunchKernelGGL(k_plan_b, dim3(B), dim3(1024), 0, st, segs, F, final_mode, cold_limit, hot_chunk, dirty,
@@ -1114,12 +1307,12 @@ hipError_t launch_accum_cold(Segs segs, Plan plan, uint32_t cold_items, State st
   // persistent: half-tile items, two 512-thread workgroups per CU; cold_items may be
   // DEV_COUNT (read on the device)
   const uint32_t g2 = std::min<uint32_t>(cold_items == DEV_COUNT ? 0xFFFFFFFFu : 2u * cold_items, 2u * (uint32_t)num_cus());
-  if (out.enc)
-    hipLaunchKernelGGL(k_accum_cold_h<true>, dim3(g2), dim3(512), ACC_COLDHE_LDS, st, segs, plan, state, tb, out,
-                       cold_items, final_mode, reset);
+  if (out.enc)  // (the sparse export: a resetting final pass)
+    hipLaunchKernelGGL(k_accum_cold_sparse, dim3(g2), dim3(COLD_NT), ColdLds<true>::bytes, st, segs, plan, state, tb,
+                       out, cold_items);
   else
-    hipLaunchKernelGGL(k_accum_cold_h<false>, dim3(g2), dim3(512), ACC_COLDH_LDS, st, segs, plan, state, tb, out,
-                       cold_items, final_mode, reset);
+    hipLaunchKernelGGL(k_accum_cold_dense, dim3(g2), dim3(COLD_NT), ColdLds<false>::bytes, st, segs, plan, state, tb,
+                       out, cold_items, final_mode, reset);
   return hipGetLastError();
 }
 
@@ -1131,10 +1324,10 @@ hipError_t launch_fold1(const uint32_t* series, const float* values, size_t n, u
   const size_t items = (n + chunk - 1) / chunk;
   const dim3 grid((uint32_t)std::min<size_t>(items, (size_t)num_cus()));
   if (state.S <= 16 && !wide)
-    hipLaunchKernelGGL(k_fold1<true>, grid, dim3(WG), FOLD16_LDS, st, series, values, n, chunk, state, tb, err,
+    hipLaunchKernelGGL(k_fold1<true>, grid, dim3(WG), Fold1Lds<true>::bytes, st, series, values, n, chunk, state, tb, err,
                        vec ? 1 : 0);
   else
-    hipLaunchKernelGGL(k_fold1<false>, grid, dim3(WG), FOLD32_LDS, st, series, values, n, chunk, state, tb, err,
+    hipLaunchKernelGGL(k_fold1<false>, grid, dim3(WG), Fold1Lds<false>::bytes, st, series, values, n, chunk, state, tb, err,
                        vec ? 1 : 0);
   return hipGetLastError();
 }
@@ -1150,7 +1343,7 @@ hipError_t launch_accum_split(Segs segs, Plan plan, uint32_t max_split_items, St
   // big tiles): every CU there measured the same on the split-heavy 8-way shards and cost
   // C2 10 us for the launch of 256 idle workgroups (profiles/r06_split_grid_ab.txt).
   const uint32_t g = std::max<uint32_t>(1u, (uint32_t)num_cus() * 3 / 8);
-  hipLaunchKernelGGL(k_accum_split, dim3(std::min<uint32_t>(max_split_items, g)), dim3(WG), ACC_SPLIT_LDS, st, segs,
+  hipLaunchKernelGGL(k_accum_split, dim3(std::min<uint32_t>(max_split_items, g)), dim3(WG), SplitLds::bytes, st, segs,
                      plan, state, tb, out, direct_out, hot_chunk);
   return hipGetLastError();
 }
