@@ -253,6 +253,51 @@ int l5dh_le(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* cuts,
 int l5dh_le_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals /* nullable */, size_t n,
                   const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate);
 
+/* State import and sparse export: the way INTO the bucket rows, and the CSR form of the way
+ * out.  Rows that left an engine -- l5dh_export_state / l5dh_export_sparse output, the slice
+ * of a merge, the g_counts of a rollup, the non-empty buckets of a peek -- enter another one:
+ * a larger engine that takes over (growth), an aggregator above the process, a restart.
+ *
+ * An import makes every target series report exactly what it would report had it also
+ * received the samples behind the imported row: counts[b] += row[b] for every bucket, the
+ * exact sum += totals[i] (an int64 that wraps like a Java long), and everything downstream
+ * (snapshot, peek, rollup, le, export, merge) sees the union.  Samples ingested before or
+ * after the call -- those still in the staging ring or in pending segments included -- are
+ * unaffected.  Domain: every imported count in [0, 2^31 - 1].  A bucket sum above 2^31 - 1 is
+ * -ERANGE, found on the device and never wrapped, l5dh_last_error naming the least such
+ * series.  A failing import leaves the observable state exactly as it was (l5dh_export_state
+ * of the whole engine is byte-identical before and after), the call's valid rows included.
+ * Every data pointer may be host or device memory.
+ *
+ * l5dh_import_state: counts [count][1798] int32 and totals [count] int64 (nullable: 0) -- what
+ * l5dh_export_state writes -- into series [first, first+count).  -EINVAL: a range out of
+ * bounds (found on the host), a negative count (found on the device; l5dh_last_error names
+ * the least such series). */
+typedef struct {
+  uint32_t bucket; /* < 1798 */
+  uint32_t count;  /* 1 .. 2^31 - 1 in an export; an imported 0 is legal and adds nothing */
+} l5dh_bucket_entry; /* 8 B */
+int l5dh_import_state(l5dh_ctx* ctx, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals);
+
+/* CSR of the non-empty buckets of series [first, first+count) (staged samples are binned and
+ * pending segments folded first): row_off [count+1] with row_off[0] = 0, row i's entries at
+ * entries[row_off[i] .. row_off[i+1]) in ascending bucket order, totals [count] (nullable) the
+ * rows' exact sums.  *n_entries always receives the exact entry count (= row_off[count]).
+ * entries == NULL is a size query: nothing else is written, nothing is reset.  cap <
+ * *n_entries is -ERANGE: nothing else is written, nothing is reset.  reset as in
+ * l5dh_export_state: the range is cleared afterwards, under the same hold of the lock. */
+int l5dh_export_sparse(l5dh_ctx* ctx, uint32_t first, uint32_t count, uint64_t* row_off,
+                       l5dh_bucket_entry* entries, size_t cap, size_t* n_entries, int64_t* totals, int reset);
+
+/* n CSR rows (row_off [n+1], entries, totals [n] nullable: 0): row i goes to series[i]
+ * (strictly ascending, each < max_series); series == NULL: to first + i.  The rows are checked
+ * on the device before any state is touched; each of these is -EINVAL, l5dh_last_error naming
+ * the least offending row: row_off not ascending from 0; an entry with bucket >= 1798; buckets
+ * not strictly ascending within a row; a count above 2^31 - 1; series not strictly ascending,
+ * or >= max_series.  first + n > max_series (series == NULL) is -EINVAL, found on the host. */
+int l5dh_import_sparse(l5dh_ctx* ctx, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
+                       const l5dh_bucket_entry* entries, const int64_t* totals);
+
 /* Java number texts, as the exporters print them (host only, no context): Long.toString,
  * the unsigned 64-bit decimal (the `le` counts) and Double.toString as JDK 8 prints it
  * (FloatingDecimal: not the shortest round-trip form of later JDKs; 2.82879384806159e17

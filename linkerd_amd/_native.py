@@ -25,6 +25,7 @@ NBUCKETS = 1798
 SUMMARY_FIELDS = ("count", "min", "max", "sum", "p50", "p90", "p95", "p99", "p9990", "p9999", "avg")
 SUMMARY_DTYPE = np.dtype([(f, "<i8") for f in SUMMARY_FIELDS[:-1]] + [("avg", "<f8")])
 BUCKET_COUNT_DTYPE = np.dtype([("lower", "<i4"), ("upper", "<i4"), ("count", "<i4")])
+BUCKET_ENTRY_DTYPE = np.dtype([("bucket", "<u4"), ("count", "<u4")])  # l5dh_bucket_entry
 
 PARAM_TIMING = 1
 PARAM_COLD_LIMIT = 2
@@ -93,6 +94,10 @@ SIGNATURES = {
     "l5dh_le_cuts": (_c.c_int, [_vp, _c.c_size_t, _vp, _vp]),
     "l5dh_le": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int, _vp, _c.c_int]),
     "l5dh_le_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
+    "l5dh_import_state": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp]),
+    "l5dh_export_sparse": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_size_t, _c.POINTER(_c.c_size_t),
+                                      _vp, _c.c_int]),
+    "l5dh_import_sparse": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_size_t, _vp, _vp, _vp]),
     "l5dh_format_double": (_c.c_int, [_c.c_double, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_long": (_c.c_int, [_c.c_int64, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_ulong": (_c.c_int, [_c.c_uint64, _vp, _c.POINTER(_c.c_size_t)]),

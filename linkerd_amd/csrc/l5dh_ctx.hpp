@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/l5dhist.h"
+#include "l5dh_import.hpp"
 #include "l5dh_kernels.hpp"
 #include "l5dh_le.hpp"
 #include "l5dh_merge.hpp"
@@ -141,6 +142,10 @@ struct l5dh_ctx {
   // label rollups (l5dh_rollup.hip): the staged map, the plan's arrays, the partial rows, staged outputs
   DevBuf ru_group, ru_u32, ru_u64, ru_members, ru_igroup, ru_mlist, ru_partial, ru_tmp, ru_summ, ru_counts, ru_totals;
   DevBuf le_stage, le_sums_stage;  // cumulative `le` buckets (l5dh_le.hip): staged outputs
+  // state import and sparse export (l5dh_import.hip): status words, staged CSR inputs, the clean
+  // tiles' flags and list; the export's row counts, offsets, scan scratch and staged entries
+  DevBuf imp_status, imp_series, imp_off, imp_entries, imp_tflag, imp_list;
+  DevBuf xs_cnt, xs_offs, xs_tmp, xs_entries;
   // the device renderer (l5dh_render.hip): staged names, values and output, the passes' scratch
   DevBuf rd_index, rd_koff, rd_kbytes, rd_loff, rd_lbytes, rd_vals, rd_sums, rd_le, rd_out;
   DevBuf rd_len, rd_offs, rd_avg, rd_flags, rd_tmp;

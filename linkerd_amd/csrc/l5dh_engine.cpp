@@ -605,6 +605,140 @@ int do_le(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const
   return sync_stream(c);
 }
 
+// ---- state import and sparse export -------------------------------------------------
+// The status words of an import, read in one copy and one wait.
+int imp_read_status(l5dh_ctx* c, uint32_t (&hs)[IS_WORDS]) {
+  HIPCHK(c, hipMemcpyAsync(hs, c->imp_status.p, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+  return sync_stream(c);
+}
+
+// Dense rows into series [first, first + count).  The caller holds the lock and has checked
+// the range; count > 0.  Nothing is flushed or folded: the ring's samples and the pending
+// segments are summed onto the rows by whichever snapshot comes next.
+int do_import_dense(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {
+  int r;
+  if ((r = ensure(c, c->imp_status, IS_WORDS * 4))) return r;
+  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_export_state)
+  if ((r = stage_in(c, counts, (size_t)count * NB, 8, c->stage_in_counts)) ||
+      (r = stage_in(c, totals, count, 8, c->stage_in_totals)))
+    return r;
+  uint32_t* status = c->imp_status.as<uint32_t>();
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, import_status_init(status, c->stream));
+    HIPCHK(c, import_dense(state(c), first, count, counts, totals, status, c->stream));
+  }
+  uint32_t hs[IS_WORDS];
+  if ((r = imp_read_status(c, hs))) return r;
+  if (hs[IS_BAD] == IS_NONE && hs[IS_RANGE] == IS_NONE) return 0;
+  {  // the same rows out again: the state reads as it did before the call
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, import_dense_undo(state(c), first, count, counts, totals, c->stream));
+  }
+  if ((r = sync_stream(c))) return r;
+  if (hs[IS_BAD] != IS_NONE)
+    return fail(c, -EINVAL, "import_state: a negative count in the row of series " + std::to_string(hs[IS_BAD]));
+  return fail(c, -ERANGE, "import_state: a bucket sum of series " + std::to_string(hs[IS_RANGE]) + " exceeds 2^31 - 1");
+}
+
+// CSR rows into the state.  The caller holds the lock; n > 0.
+int do_import_sparse(l5dh_ctx* c, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
+                     const BucketEntry* entries, const int64_t* totals) {
+  int r;
+  if (!row_off) return fail(c, -EINVAL, "import_sparse: null row_off");
+  if (n > c->S) return fail(c, -EINVAL, "import_sparse: more rows than series");
+  if (!series && (uint64_t)first + n > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  // the entry count: row_off[n] (a device array: one small copy and wait)
+  uint64_t n_entries = 0;
+  if (is_device_ptr(row_off)) {
+    HIPCHK(c, hipMemcpyAsync(&n_entries, row_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+    if ((r = sync_stream(c))) return r;
+  } else {
+    memcpy(&n_entries, row_off + n, 8);
+  }
+  if (n_entries && !entries) return fail(c, -EINVAL, "import_sparse: null entries");
+  // more entries than n full rows: some row's offsets are wrong -- the check finds the least
+  // such row from the offsets alone (no entry is staged or read)
+  const bool offsets_only = n_entries > (uint64_t)n * NB;
+  if (offsets_only) entries = nullptr;
+  if ((r = ensure(c, c->imp_status, IS_WORDS * 4)) || (r = ensure(c, c->imp_tflag, (size_t)c->F * 4)) ||
+      (r = ensure(c, c->imp_list, (size_t)c->F * 4)))
+    return r;
+  if ((r = stage_in(c, series, n, 4, c->imp_series)) || (r = stage_in(c, row_off, n + 1, 8, c->imp_off)) ||
+      (r = stage_in(c, entries, (size_t)n_entries, 8, c->imp_entries)) ||
+      (r = stage_in(c, totals, n, 8, c->stage_in_totals)))
+    return r;
+  const SparseRows rows{series, first, (uint32_t)n, row_off, entries, totals, n_entries};
+  uint32_t* status = c->imp_status.as<uint32_t>();
+  uint32_t hs[IS_WORDS];
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, import_status_init(status, c->stream));
+    HIPCHK(c, import_sparse_check(rows, c->S, status, c->stream));
+  }
+  // no state is touched before the host has read the check's findings
+  if ((r = imp_read_status(c, hs))) return r;
+  if (hs[IS_BAD] != IS_NONE)
+    return fail(c, -EINVAL,
+                "import_sparse: row " + std::to_string(hs[IS_BAD]) +
+                    " is invalid (offsets, series id, bucket order or range, or a count above 2^31 - 1)");
+  if (offsets_only) return fail(c, -EIO, "internal: import_sparse offsets");
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, import_sparse(state(c), rows, c->imp_tflag.as<uint32_t>(), c->imp_list.as<uint32_t>(), status, c->stream));
+  }
+  if ((r = imp_read_status(c, hs))) return r;
+  if (hs[IS_RANGE] == IS_NONE) return 0;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, import_sparse_undo(state(c), rows, c->stream));
+  }
+  if ((r = sync_stream(c))) return r;
+  return fail(c, -ERANGE, "import_sparse: a bucket sum of series " + std::to_string(hs[IS_RANGE]) + " exceeds 2^31 - 1");
+}
+
+// The CSR of the non-empty buckets of series [first, first + count).  The caller holds the
+// lock and has checked the arguments; count > 0.
+int do_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_off, BucketEntry* entries, size_t cap,
+                     size_t* n_entries, int64_t* totals, int reset) {
+  int r;
+  if ((r = flush_ring(c)) || (r = fold(c))) return r;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, merge_count(nullptr, count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
+      (r = ensure(c, c->xs_tmp, tmp_bytes)))
+    return r;
+  uint64_t* offs = c->xs_offs.as<uint64_t>();
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, export_sparse_count(state(c), first, count, c->xs_cnt.as<uint32_t>(), c->stream));
+    HIPCHK(c, merge_count(nullptr, count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
+  }
+  // the entry count: one host wait, before anything of the caller's is written
+  uint64_t total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, offs + count, 8, hipMemcpyDeviceToHost, c->stream));
+  if ((r = sync_stream(c))) return r;
+  *n_entries = (size_t)total;
+  if (!entries) return 0;  // a size query
+  if (cap < total)
+    return fail(c, -ERANGE, "export_sparse: " + std::to_string(total) + " entries, room for " + std::to_string(cap));
+  StagedOut<BucketEntry> ent;
+  StagedOut<int64_t> tot;
+  if ((r = ent.begin(c, entries, (size_t)total, c->xs_entries)) || (r = tot.begin(c, totals, count, c->stage_totals)))
+    return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, export_sparse_write(state(c), first, count, offs, ent.dev, tot.dev, c->stream));
+    // the reset of the same range, from the same state
+    if (reset)
+      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{nullptr, nullptr, first, count, nullptr}, reset,
+                            nullptr, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(row_off, offs, ((size_t)count + 1) * 8, hipMemcpyDefault, c->stream));
+  if ((r = ent.end(c)) || (r = tot.end(c))) return r;  // (the copies are not timed here)
+  return sync_stream(c);
+}
+
 // ---- the device renderer -----------------------------------------------------------
 // Bytes of a name array that is not used in place: its offsets' last entry (the write
 // pass, the only reader of the bytes, runs after every offset was found ascending).
@@ -936,6 +1070,44 @@ int l5dh_le_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, siz
   if (n == 0) return 0;
   if (!counts || !le_out) return fail(c, -EINVAL, "le: null dense rows or output");
   return do_le(c, 0, (uint32_t)n, counts, totals, lc, ncuts, le_out, sums_out, accumulate, nullptr, 0);
+}
+
+int l5dh_import_state(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (count == 0) return 0;
+  if (!counts) return fail(c, -EINVAL, "import_state: null counts");
+  return do_import_dense(c, first, count, counts, totals);
+}
+
+int l5dh_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_off, l5dh_bucket_entry* entries,
+                       size_t cap, size_t* n_entries, int64_t* totals, int reset) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (!n_entries) return fail(c, -EINVAL, "export_sparse: null n_entries");
+  if (entries && !row_off) return fail(c, -EINVAL, "export_sparse: null row_off");
+  if (count == 0) {
+    *n_entries = 0;
+    if (entries) {  // (an empty range still has its row_off[0] = 0)
+      const uint64_t zero = 0;
+      HIPCHK(c, hipMemcpyAsync(row_off, &zero, 8, hipMemcpyDefault, c->stream));
+      return sync_stream(c);
+    }
+    return 0;
+  }
+  static_assert(sizeof(l5dh_bucket_entry) == sizeof(BucketEntry), "l5dh_bucket_entry layout");
+  return do_export_sparse(c, first, count, row_off, reinterpret_cast<BucketEntry*>(entries), cap, n_entries, totals,
+                          reset);
+}
+
+int l5dh_import_sparse(l5dh_ctx* c, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
+                       const l5dh_bucket_entry* entries, const int64_t* totals) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (n == 0) return 0;
+  return do_import_sparse(c, series, first, n, row_off, reinterpret_cast<const BucketEntry*>(entries), totals);
 }
 
 int l5dh_format_double(double x, char* out, size_t* len) {

@@ -212,6 +212,115 @@ class HistogramEngine:
         self._check(self._lib.l5dh_export_state(self._ctx, first, count, cp, tp, int(reset)), "l5dh_export_state")
         return (counts, totals) if own else None
 
+    # -- state import and sparse export ---------------------------------------------
+    def import_state(self, counts, totals=None, first: int = 0) -> None:
+        """l5dh_import_state: dense rows (counts int32 [count][1798], totals int64 [count]
+        or None: 0 -- what ``export_state`` returns; numpy, or torch tensors on the engine's
+        GPU) are added to series [first, first+count): each then reports what it would had
+        it also received the samples behind its row.  A bucket sum above 2^31 - 1 raises
+        (ERANGE), a negative count raises (EINVAL); a failing import changes nothing."""
+        count = _numel(counts) // N.NBUCKETS
+        if count * N.NBUCKETS != _numel(counts):
+            raise ValueError("counts must hold whole rows of 1798 buckets")
+        first = int(first)
+        if first < 0 or first >= 2 ** 32:
+            raise ValueError(f"first={first} does not fit uint32")
+        cp = self._buf(counts, (np.int32,), "counts")
+        tp = self._buf(totals, (np.int64,), "totals", count)
+        self._check(self._lib.l5dh_import_state(self._ctx, first, count, cp, tp), "l5dh_import_state")
+
+    def _entry_buf(self, x, n: int, name: str, writable: bool = False):
+        """Pointer of ``n`` l5dh_bucket_entry: a numpy array of N.BUCKET_ENTRY_DTYPE, or a
+        numpy array / torch tensor of 2n uint32 (int32) or n uint64 (int64) words."""
+        if x is None:
+            return None
+        if isinstance(x, np.ndarray) and x.dtype == N.BUCKET_ENTRY_DTYPE:
+            if x.size < n or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
+                raise ValueError(f"{name}: needs {n} contiguous{' writable' if writable else ''} bucket entries")
+            return x.ctypes.data
+        dt = x.dtype.type if isinstance(x, np.ndarray) else _NP_OF_TORCH.get(str(getattr(x, "dtype", None)))
+        if dt in (np.uint64, np.int64):
+            return self._buf(x, (np.uint64, np.int64), name, n, writable=writable)
+        return self._buf(x, (np.uint32, np.int32), name, 2 * n, writable=writable)
+
+    def export_sparse_size(self, first: int = 0, count: Optional[int] = None) -> int:
+        """The entries ``export_sparse`` of the range would write (the size query)."""
+        first, count = self._range(first, count)
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.l5dh_export_sparse(self._ctx, first, count, None, None, 0, ctypes.byref(n), None, 0),
+                    "l5dh_export_sparse")
+        return n.value
+
+    def export_sparse_into(self, row_off, entries, totals=None, first: int = 0, count: Optional[int] = None,
+                           reset: bool = False) -> int:
+        """l5dh_export_sparse into caller buffers (numpy, or torch tensors on the engine's
+        GPU): row_off uint64 (int64) [count+1], entries (N.BUCKET_ENTRY_DTYPE, or uint32
+        [cap][2], or 64-bit words [cap]), totals int64 [count] or None.  Returns the entry
+        count; entries too small for it raise ERANGE with nothing written or reset."""
+        first, count = self._range(first, count)
+        rp = self._buf(row_off, (np.uint64, np.int64), "row_off", count + 1, writable=True)
+        if row_off is None or entries is None:
+            raise ValueError("row_off and entries: output buffers are needed (export_sparse_size is the size query)")
+        if isinstance(entries, np.ndarray) and entries.dtype == N.BUCKET_ENTRY_DTYPE:
+            cap = int(entries.size)
+        else:
+            words64 = (entries.dtype.type if isinstance(entries, np.ndarray)
+                       else _NP_OF_TORCH.get(str(entries.dtype))) in (np.uint64, np.int64)
+            cap = _numel(entries) if words64 else _numel(entries) // 2
+        ep = self._entry_buf(entries, 0, "entries", writable=True)
+        tp = self._buf(totals, (np.int64,), "totals", count, writable=True)
+        n = ctypes.c_size_t(0)
+        self._check(self._lib.l5dh_export_sparse(self._ctx, first, count, rp, ep, cap, ctypes.byref(n), tp,
+                                                 int(reset)), "l5dh_export_sparse")
+        return n.value
+
+    def export_sparse(self, first: int = 0, count: Optional[int] = None, reset: bool = False):
+        """(row_off uint64 [count+1], entries N.BUCKET_ENTRY_DTYPE [row_off[count]], totals
+        int64 [count]): the CSR of the non-empty buckets of series [first, first+count), row
+        i's entries at entries[row_off[i]:row_off[i+1]] in ascending bucket order.  ``reset``
+        clears the range afterwards, atomically with the export."""
+        first, count = self._range(first, count)
+        row_off, totals = np.zeros(count + 1, np.uint64), np.zeros(count, np.int64)
+        # (the size query and the export are two holds of the lock: samples that arrive in
+        # between make the buffer too small, and the export is tried again)
+        while True:
+            entries = np.zeros(max(1, self.export_sparse_size(first, count)), N.BUCKET_ENTRY_DTYPE)
+            n = ctypes.c_size_t(0)
+            rc = self._lib.l5dh_export_sparse(self._ctx, first, count, row_off.ctypes.data, entries.ctypes.data,
+                                              entries.size, ctypes.byref(n), totals.ctypes.data, int(reset))
+            if rc == -errno.ERANGE and n.value > entries.size:
+                continue
+            self._check(rc, "l5dh_export_sparse")
+            return row_off, entries[:n.value], totals
+
+    def import_sparse(self, row_off, entries, totals=None, first: int = 0, series=None) -> None:
+        """l5dh_import_sparse: CSR rows (what ``export_sparse`` returns) are added to series
+        ``series[i]`` (uint32, strictly ascending) or, without a map, first + i.  Invalid rows
+        raise (EINVAL) and a bucket sum above 2^31 - 1 raises (ERANGE), the least offender
+        named; a failing import changes nothing."""
+        n = _numel(row_off) - 1
+        if n < 0:
+            raise ValueError("row_off: at least one offset (row_off[0] = 0) is needed")
+        first = int(first)
+        if first < 0 or first >= 2 ** 32:
+            raise ValueError(f"first={first} does not fit uint32")
+        if isinstance(series, np.ndarray) and series.dtype != np.dtype(np.uint32):
+            if series.size and (series.dtype.kind not in "iu" or series.min() < 0 or series.max() >= 2 ** 32):
+                raise ValueError("series ids must fit uint32")
+            series = np.ascontiguousarray(series.astype(np.uint32))
+        sp = self._buf(series, (np.uint32, np.int32), "series", n)
+        if series is not None and _numel(series) != n:
+            raise ValueError(f"series: {_numel(series)} ids for {n} rows")
+        rp = self._buf(row_off, (np.uint64, np.int64), "row_off")
+        if isinstance(row_off, np.ndarray) and isinstance(entries, np.ndarray):
+            # (the library reads row_off[n] entries: a host array is checked to hold them)
+            have = entries.size if entries.dtype == N.BUCKET_ENTRY_DTYPE else entries.nbytes // 8
+            if int(np.asarray(row_off).reshape(-1)[n].astype(np.uint64)) > have:
+                raise ValueError(f"entries: row_off[{n}] = {int(row_off.reshape(-1)[n])} entries, {have} given")
+        ep = self._entry_buf(entries, 0, "entries") if entries is not None and _numel(entries) else None
+        tp = self._buf(totals, (np.int64,), "totals", n)
+        self._check(self._lib.l5dh_import_sparse(self._ctx, sp, first, n, rp, ep, tp), "l5dh_import_sparse")
+
     def summarize_dense(self, counts, totals, out=None):
         n = _numel(counts) // N.NBUCKETS
         if n * N.NBUCKETS != _numel(counts):

@@ -111,6 +111,92 @@ class StatEngine:
         """Series ids currently held by Stats."""
         return self._next - len(self._free)
 
+    # growth and restart: the open interval moves as sparse rows (export_sparse -> import_sparse)
+    def grow(self, capacity: int) -> None:
+        """Make room for ``capacity`` series: a larger HistogramEngine takes over the open
+        interval of this one (its rows leave with export_sparse(reset=True) and enter with
+        import_sparse, so they cost what the data costs, not 7192 B per series), the ids
+        held by Stats stay valid, and register() succeeds again.  The lifetime ``le``
+        counters are kept and extended with zero rows.  Adds from other threads wait for the
+        swap; snapshot calls must not run beside it.  Tunables set on the old engine
+        (HistogramEngine.set_param) are not carried over."""
+        capacity = int(capacity)
+        self.flush()
+        with self._lock:
+            if capacity <= self.capacity:
+                raise ValueError(f"grow: capacity {capacity} is not above {self.capacity}")
+            bufs = list(self._buffers)
+            for st in bufs:  # every thread's adds wait until the new engine is in place
+                st.lock.acquire()
+            try:
+                for st in bufs:
+                    self._flush_locked(st)
+                old = self.engine
+                new = type(old)(capacity, old.device)
+                try:
+                    row_off, entries, totals = old.export_sparse(first=0, count=self._next, reset=True)
+                    new.import_sparse(row_off, entries, totals, first=0)
+                except Exception:
+                    new.close()
+                    raise
+                self.engine, self.capacity = new, int(new.max_series)
+                if self.le_cuts is not None:
+                    K1 = self.le_buckets.shape[1]
+                    more = self.capacity - self.le_buckets.shape[0]
+                    self.le_buckets = np.concatenate([self.le_buckets, np.zeros((more, K1), np.uint64)])
+                    self.le_sums = np.concatenate([self.le_sums, np.zeros(more, np.int64)])
+                old.close()
+            finally:
+                for st in bufs:
+                    st.lock.release()
+
+    def checkpoint(self, reset: bool = False) -> Dict[str, np.ndarray]:
+        """The open interval and the registry as numpy arrays (np.savez takes the dict as it
+        is): the sparse rows and totals of every id handed out so far, the next id, the
+        free list, and the ``le`` cuts, labels and lifetime counters.  ``reset`` ends the
+        interval here (what a process does before it stops)."""
+        self.flush()
+        with self._lock:
+            n = self._next
+            row_off, entries, totals = self.engine.export_sparse(first=0, count=n, reset=reset)
+            le = self.le_cuts is not None
+            K1 = self.le_buckets.shape[1] if le else 1
+            return {
+                "row_off": row_off, "entries": entries, "totals": totals,
+                "next": np.array([n], np.int64), "free": np.array(self._free, np.uint32),
+                "le_cuts": self.le_cuts.copy() if le else np.zeros(0, np.uint32),
+                "le_labels": self.le_labels.copy() if le else np.zeros(0, np.int64),
+                "le_buckets": self.le_buckets[:n].copy() if le else np.zeros((0, K1), np.uint64),
+                "le_sums": self.le_sums[:n].copy() if le else np.zeros(0, np.int64),
+            }
+
+    def restore(self, ckpt) -> None:
+        """Take over a checkpoint: on a fresh StatEngine (no id handed out yet) of at least
+        the checkpoint's ids.  Afterwards the engine reports what the checkpointed one
+        did, and register() continues where it stopped."""
+        from . import _native as N
+        n = int(np.asarray(ckpt["next"]).reshape(-1)[0])
+        with self._lock:
+            if self._next != 0 or self._free:
+                raise RuntimeError("restore needs a fresh StatEngine")
+            if n > self.capacity:
+                raise ValueError(f"restore: the checkpoint holds {n} series, the engine {self.capacity}")
+            row_off = np.ascontiguousarray(ckpt["row_off"], np.uint64)
+            entries = np.ascontiguousarray(ckpt["entries"]).view(N.BUCKET_ENTRY_DTYPE).reshape(-1)
+            totals = np.ascontiguousarray(ckpt["totals"], np.int64)
+            if row_off.size != n + 1 or totals.size != n or int(row_off[-1]) != entries.size:
+                raise ValueError("restore: the checkpoint's arrays do not belong together")
+            self.engine.import_sparse(row_off, entries, totals, first=0)
+            self._next = n
+            self._free = [int(x) for x in np.asarray(ckpt["free"]).reshape(-1)]
+            cuts = np.asarray(ckpt["le_cuts"], np.uint32).reshape(-1)
+            if cuts.size:
+                self.le_cuts, self.le_labels = cuts.copy(), np.asarray(ckpt["le_labels"], np.int64).reshape(-1).copy()
+                self.le_buckets = np.zeros((self.capacity, cuts.size + 1), np.uint64)
+                self.le_sums = np.zeros(self.capacity, np.int64)
+                self.le_buckets[:n] = np.asarray(ckpt["le_buckets"], np.uint64).reshape(n, cuts.size + 1)
+                self.le_sums[:n] = np.asarray(ckpt["le_sums"], np.int64).reshape(-1)
+
     def _staging(self) -> "_Staging":
         st = getattr(self._tls, "st", None)
         if st is None:
