@@ -253,6 +253,39 @@ int l5dh_le(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* cuts,
 int l5dh_le_dense(l5dh_ctx* ctx, const int32_t* counts, const int64_t* totals /* nullable */, size_t n,
                   const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate);
 
+/* Exact configurable quantiles: the inverse of the `le` buckets -- not "how many samples lie
+ * at or below this value" but "which value is the q-quantile", for any q in [0, 1] (p25 and
+ * p75 of a box plot, the p99.5 of an SLO, the p99.99 of a rollup group), without the dense
+ * rows leaving the device.  Upstream BucketedHistogram.percentile(q): for a row with bucket
+ * counts c[0..1797] and num = c[0] + ... + c[1797] (64 bits),
+ *   target = Math.round(q * (double)num)      one FP64 product, JDK-8 Math.round
+ *   target == 0 -> 0                          q = 0, an empty row, or q * num < 0.5
+ *   else the midpoint of the first bucket whose running count >= target (the overflow
+ *   bucket reports Int.MaxValue).
+ * For q = 0.5, 0.9, 0.95, 0.99, 0.999, 0.9999 this is the summary's field; for q = 1 and a
+ * non-empty row it is max; q = 0 gives 0, which is not min.  The order of the q is free and
+ * duplicates are legal.
+ *
+ * l5dh_quantiles: live state.  Under ONE hold of the context lock: staged samples are binned
+ * and pending segments folded; per series i of [first, first+count) the nq values go to
+ * q_out[i][0..nq-1] (int64 [count][nq]); then, if series_out is given and/or reset != 0, the
+ * per-series snapshot of the same range is taken from the same state (series_out: count
+ * l5dh_summary, nullable) and the range is cleared -- the quantiles, the summaries and the
+ * reset all see exactly the same samples.  Every pointer may be host or device memory (q
+ * included).  count == 0 returns 0 and writes nothing.
+ * -EINVAL, with nothing written and nothing reset: nq outside [1, L5DH_Q_MAX], a q that is
+ * NaN, < 0 or > 1 (upstream's AssertionError; found on the host before anything is
+ * enqueued), a bad range, a null q / q_out. */
+#define L5DH_Q_MAX 64 /* quantiles per call */
+int l5dh_quantiles(l5dh_ctx* ctx, uint32_t first, uint32_t count, const double* q, uint32_t nq,
+                   int64_t* q_out /* [count][nq] */, l5dh_summary* series_out /* nullable */, int reset);
+
+/* The same over external dense rows: counts [n][1798] int32 -- the inputs and the domain of
+ * l5dh_summarize_dense (every count in [0, 2^31 - 1], any row sum).  E.g. the g_counts of a
+ * rollup: the exact quantiles of the members' union. */
+int l5dh_quantiles_dense(l5dh_ctx* ctx, const int32_t* counts, size_t n, const double* q, uint32_t nq,
+                         int64_t* q_out /* [n][nq] */);
+
 /* State import and sparse export: the way INTO the bucket rows, and the CSR form of the way
  * out.  Rows that left an engine -- l5dh_export_state / l5dh_export_sparse output, the slice
  * of a merge, the g_counts of a rollup, the non-empty buckets of a peek -- enter another one:
@@ -330,13 +363,19 @@ int l5dh_format_ulong(uint64_t v, char* out /* >= L5DH_LONG_CHARS */, size_t* le
  *   ncuts lines key_hist_bucket{.. le="<le[k]>"} n, one with le="+Inf" carrying the last
  *   column, key_hist_sum lab s, key_hist_count lab <the last column> -- n as
  *   l5dh_format_ulong.
+ * l5dh_render_quantiles prints per row, from q_rows[index[j]][0..nq-1] (what l5dh_quantiles
+ * wrote; int64 [nvalues][nq]):
+ *   nq lines key{.. quantile="<l5dh_format_double(q[k])>"} N -- 0.75, 0.995, 1.0E-4 -- N as
+ *   l5dh_format_long.  The labels are formatted once per call on the host; q is checked as
+ *   l5dh_quantiles checks it (-EINVAL), and a q outside l5dh_format_double's domain (a
+ *   positive q below 2^-64) is -ERANGE, both before anything is enqueued.
  *
  * Every data pointer (the five arrays of the table included) may be host or device
  * memory.  *len always receives the exact length of the text.  out == NULL is a size
  * query (returns 0); out != NULL with cap < *len is -ERANGE and nothing is written;
  * n == 0 writes nothing, sets *len = 0 and returns 0.  -EINVAL: ncuts outside
- * [1, L5DH_LE_MAX], a null names, key_off, lab_off or le, nvalues == 0 (or null values)
- * with n > 0.  Found on the device and reported by the call, l5dh_last_error naming the
+ * [1, L5DH_LE_MAX], nq outside [1, L5DH_Q_MAX], a null names, key_off, lab_off, le or q,
+ * nvalues == 0 (or null values) with n > 0.  Found on the device and reported by the call, l5dh_last_error naming the
  * first such row, the output then unspecified: index[j] >= nvalues, offsets that descend,
  * a row whose key and label text exceed 2^25 bytes (-EINVAL); an avg outside
  * l5dh_format_double's domain (-ERANGE).  The calls read no engine state: they hold the
@@ -353,6 +392,8 @@ int l5dh_render_summaries(l5dh_ctx* ctx, const l5dh_names* names, size_t n, cons
 int l5dh_render_le(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const uint64_t* le_rows,
                    const int64_t* sums /* nullable: 0 */, size_t nvalues, const int64_t* le, uint32_t ncuts,
                    uint8_t* out, size_t cap, size_t* len);
+int l5dh_render_quantiles(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const int64_t* q_rows /* [nvalues][nq] */,
+                          size_t nvalues, const double* q, uint32_t nq, uint8_t* out, size_t cap, size_t* len);
 
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:

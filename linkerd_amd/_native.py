@@ -43,6 +43,7 @@ PARAM_ROLLUP_ITEM = 14
 NO_GROUP = 0xFFFFFFFF  # L5DH_NO_GROUP
 MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
 LE_MAX = 64  # L5DH_LE_MAX
+Q_MAX = 64  # L5DH_Q_MAX
 DOUBLE_CHARS = 26  # L5DH_DOUBLE_CHARS
 LONG_CHARS = 20  # L5DH_LONG_CHARS
 
@@ -94,6 +95,8 @@ SIGNATURES = {
     "l5dh_le_cuts": (_c.c_int, [_vp, _c.c_size_t, _vp, _vp]),
     "l5dh_le": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int, _vp, _c.c_int]),
     "l5dh_le_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
+    "l5dh_quantiles": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
+    "l5dh_quantiles_dense": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp]),
     "l5dh_import_state": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp]),
     "l5dh_export_sparse": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_size_t, _c.POINTER(_c.c_size_t),
                                       _vp, _c.c_int]),
@@ -105,6 +108,8 @@ SIGNATURES = {
                                          _c.POINTER(_c.c_size_t)]),
     "l5dh_render_le": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _c.c_size_t,
                                   _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_quantiles": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _c.c_size_t,
+                                         _c.POINTER(_c.c_size_t)]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

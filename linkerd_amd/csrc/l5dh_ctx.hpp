@@ -17,6 +17,7 @@
 #include "l5dh_kernels.hpp"
 #include "l5dh_le.hpp"
 #include "l5dh_merge.hpp"
+#include "l5dh_quant.hpp"
 #include "l5dh_render.hpp"
 #include "l5dh_rollup.hpp"
 
@@ -142,6 +143,8 @@ struct l5dh_ctx {
   // label rollups (l5dh_rollup.hip): the staged map, the plan's arrays, the partial rows, staged outputs
   DevBuf ru_group, ru_u32, ru_u64, ru_members, ru_igroup, ru_mlist, ru_partial, ru_tmp, ru_summ, ru_counts, ru_totals;
   DevBuf le_stage, le_sums_stage;  // cumulative `le` buckets (l5dh_le.hip): staged outputs
+  DevBuf q_stage;                  // configurable quantiles (l5dh_quant.hip): staged output
+  DevBuf rd_qlabels;               // the device renderer's quantile labels, formatted on the host
   // state import and sparse export (l5dh_import.hip): status words, staged CSR inputs, the clean
   // tiles' flags and list; the export's row counts, offsets, scan scratch and staged entries
   DevBuf imp_status, imp_series, imp_off, imp_entries, imp_tflag, imp_list;

@@ -605,6 +605,52 @@ int do_le(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const
   return sync_stream(c);
 }
 
+// ---- configurable quantiles ---------------------------------------------------------
+// The quantiles of a call, on the host and checked: K in [1, Q_MAX], each q in [0, 1]
+// (NaN fails both comparisons).  A device array is fetched first (one small copy and wait).
+int quant_fetch_q(l5dh_ctx* c, const double* q, uint32_t nq, QuantQ& out) {
+  if (nq < 1 || nq > Q_MAX) return fail(c, -EINVAL, "quantiles: nq must be in [1, 64]");
+  if (!q) return fail(c, -EINVAL, "quantiles: null q");
+  memset(&out, 0, sizeof(out));
+  if (is_device_ptr(q)) {
+    HIPCHK(c, hipMemcpyAsync(out.q, q, (size_t)nq * 8, hipMemcpyDeviceToHost, c->stream));
+    if (int r = sync_stream(c)) return r;
+  } else {
+    memcpy(out.q, q, (size_t)nq * 8);
+  }
+  for (uint32_t k = 0; k < nq; ++k)
+    if (!(out.q[k] >= 0.0 && out.q[k] <= 1.0))
+      return fail(c, -EINVAL, "quantiles: q[" + std::to_string(k) + "] is not in [0, 1]");
+  return 0;
+}
+
+// The quantiles of the live state rows of series [first, first + count) (ext == nullptr;
+// then also the per-series snapshot / reset of the same state) or of external dense rows
+// ext[count][1798].  The caller holds the lock and has checked the arguments; count > 0.
+int do_quant(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const QuantQ& qs, uint32_t K,
+             int64_t* q_out, l5dh_summary* series_out, int reset) {
+  int r;
+  const bool live = ext == nullptr;
+  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
+  StagedOut<int64_t> qo;
+  StagedOut<Summary88> s_summ;
+  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_le)
+  if ((r = stage_in(c, ext, (size_t)count * NB, 8, c->stage_in_counts)) ||
+      (r = qo.begin(c, q_out, (size_t)count * K, c->q_stage)) ||
+      (r = s_summ.begin(c, series_out, count, c->stage_summ)))
+    return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, launch_quant(state(c), first, count, ext, qs, K, tables(c).mid, qo.dev, c->stream));
+    // the per-series snapshot and the reset of the same range, from the same state
+    if (live && (s_summ.dev || reset))
+      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{s_summ.dev, nullptr, first, count, nullptr},
+                            reset, nullptr, c->stream));
+  }
+  if ((r = qo.end(c)) || (r = s_summ.end(c))) return r;
+  return sync_stream(c);
+}
+
 // ---- state import and sparse export -------------------------------------------------
 // The status words of an import, read in one copy and one wait.
 int imp_read_status(l5dh_ctx* c, uint32_t (&hs)[IS_WORDS]) {
@@ -1072,6 +1118,29 @@ int l5dh_le_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, siz
   return do_le(c, 0, (uint32_t)n, counts, totals, lc, ncuts, le_out, sums_out, accumulate, nullptr, 0);
 }
 
+int l5dh_quantiles(l5dh_ctx* c, uint32_t first, uint32_t count, const double* q, uint32_t nq, int64_t* q_out,
+                   l5dh_summary* series_out, int reset) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  QuantQ qs;
+  if (int r = quant_fetch_q(c, q, nq, qs)) return r;
+  if (count == 0) return 0;
+  if (!q_out) return fail(c, -EINVAL, "quantiles: null output");
+  return do_quant(c, first, count, nullptr, qs, nq, q_out, series_out, reset);
+}
+
+int l5dh_quantiles_dense(l5dh_ctx* c, const int32_t* counts, size_t n, const double* q, uint32_t nq, int64_t* q_out) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (n > 0xFFFFFFFFull) return fail(c, -EINVAL, "quantiles: more than 2^32 - 1 dense rows");
+  QuantQ qs;
+  if (int r = quant_fetch_q(c, q, nq, qs)) return r;
+  if (n == 0) return 0;
+  if (!counts || !q_out) return fail(c, -EINVAL, "quantiles: null dense rows or output");
+  return do_quant(c, 0, (uint32_t)n, counts, qs, nq, q_out, nullptr, 0);
+}
+
 int l5dh_import_state(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {
   if (!c) return -EINVAL;
   CtxLock g(c);
@@ -1160,6 +1229,37 @@ int l5dh_render_le(l5dh_ctx* c, const l5dh_names* names, size_t n, const uint64_
       return r;
   }
   return do_render(c, names, n, nvalues, LeRows{le_rows, sums, le, ncuts}, out, cap, len);
+}
+
+int l5dh_render_quantiles(l5dh_ctx* c, const l5dh_names* names, size_t n, const int64_t* q_rows, size_t nvalues,
+                          const double* q, uint32_t nq, uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (len) *len = 0;
+  QuantQ qs;
+  int r = quant_fetch_q(c, q, nq, qs);
+  if (r) return r;
+  // the K labels, formatted once per call: Double.toString(q[k]), its length in the slot's last byte
+  uint8_t labels[Q_MAX * RENDER_QLABEL_SLOT] = {0};
+  static_assert(L5DH_DOUBLE_CHARS < RENDER_QLABEL_SLOT, "a label and its length share a slot");
+  for (uint32_t k = 0; k < nq; ++k) {
+    uint8_t* slot = labels + (size_t)k * RENDER_QLABEL_SLOT;
+    const int m = fmt::format_double(qs.q[k], reinterpret_cast<char*>(slot));
+    if (m < 0)
+      return fail(c, -ERANGE, "render: q[" + std::to_string(k) + "] is outside +-[2^-64, 2^64), 0, NaN, Infinity");
+    slot[RENDER_QLABEL_SLOT - 1] = (uint8_t)m;
+  }
+  r = rd_check(c, names, n, q_rows, nvalues, len);
+  if (r) return r < 0 ? r : 0;
+  const uint8_t* lab = labels;
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = stage_in(c, q_rows, nvalues * (size_t)nq, 8, c->rd_vals)) ||
+        (r = stage_in(c, lab, (size_t)nq * RENDER_QLABEL_SLOT, 1, c->rd_qlabels)))
+      return r;
+  }
+  // (labels lives on this frame: do_render returns only after the stream has drained)
+  return do_render(c, names, n, nvalues, QuantRows{q_rows, lab, nq}, out, cap, len);
 }
 
 int l5dh_peek(l5dh_ctx* c, uint32_t series, l5dh_bucket_count* out, size_t cap, size_t* n_out) {

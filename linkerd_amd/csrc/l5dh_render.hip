@@ -3,9 +3,9 @@
 // A row's block is a list of lines, each
 //     key sfx [ `{` inner [`, `] ext ev `"` `}` ] ` ` number `\n`
 // with key / inner the row's name bytes, sfx / ext / ev small constant texts (or, for ev,
-// an `le` label) and number a Java long, an unsigned 64-bit decimal or the avg's
-// Double.toString.  prometheus.py's write_metrics, write_rollup_metrics and
-// write_histogram_metrics print exactly these lines.
+// an `le` label or a quantile's label) and number a Java long, an unsigned 64-bit decimal or the avg's
+// Double.toString.  prometheus.py's write_metrics, write_rollup_metrics,
+// write_histogram_metrics and write_quantile_metrics print exactly these lines.
 //
 //   k_rd_len    a lane per row: checks the row (index, offsets, name length), formats its
 //               avg once into the row's 32-byte slot, and adds up the lines' lengths from
@@ -28,6 +28,7 @@ namespace {
 
 constexpr uint32_t RD_STAGE = 4096;               // bytes of a row built in LDS
 constexpr uint32_t RD_LINES_MAX = LE_MAX + 3;     // K buckets, +Inf, _sum, _count
+static_assert(Q_MAX <= RD_LINES_MAX && 11u <= RD_LINES_MAX, "a block's lines have their places in LDS");
 constexpr uint32_t RD_GRID_MAX = 256 * 32;        // one-wave workgroups of the write pass
 
 enum { NUM_LONG = 0, NUM_ULONG = 1, NUM_TEXT = 2 };
@@ -97,7 +98,7 @@ __device__ __forceinline__ void line_write(uint8_t* dst, uint32_t pos, uint32_t 
   dst[p] = '\n';
 }
 
-// ---- the two blocks ---------------------------------------------------------------
+// ---- the three blocks -------------------------------------------------------------
 // Summary: _count, _sum, _avg, then QUANTILES' eight lines (min, p50, .., p9999, max).
 struct SummaryBlock {
   SummaryRows r;
@@ -146,6 +147,28 @@ struct LeBlock {
     L.ev_num = t < K ? r.le[t] : 0;
     L.kind = t == K + 1u ? NUM_LONG : NUM_ULONG;
     L.v = t == K + 1u ? (r.sums ? (uint64_t)r.sums[idx] : 0ull) : row[t < K ? t : K];
+    L.text = nullptr;
+    L.text_n = 0u;
+  }
+};
+
+// Configured quantiles: K lines with quantile="<label>", the label the quantile's
+// Double.toString -- bytes the host formatted once per call, in global memory.
+struct QuantileBlock {
+  QuantRows r;
+  __device__ __forceinline__ uint32_t nlines() const { return r.K; }
+  __device__ __forceinline__ bool prepare(uint32_t, uint32_t) const { return true; }
+  __device__ __forceinline__ void line(uint32_t, uint32_t idx, uint32_t t, Line& L) const {
+    const uint8_t* slot = r.labels + (size_t)t * RENDER_QLABEL_SLOT;
+    L.sfx = "";
+    L.sfx_n = 0u;
+    L.ext = "quantile=\"";
+    L.ext_n = 10u;
+    L.ev = reinterpret_cast<const char*>(slot);
+    L.ev_n = slot[RENDER_QLABEL_SLOT - 1];
+    L.ev_num = 0;
+    L.kind = NUM_LONG;
+    L.v = (uint64_t)r.q_rows[(size_t)idx * r.K + t];
     L.text = nullptr;
     L.text_n = 0u;
   }
@@ -306,6 +329,11 @@ hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, c
   if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
   return lengths(nm, n, nvalues, LeBlock{rows}, len, flags, st);
 }
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const QuantRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
+  return lengths(nm, n, nvalues, QuantileBlock{rows}, len, flags, st);
+}
 hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
                         uint32_t* flags, hipStream_t st) {
   return write(nm, n, SummaryBlock{rows}, offs, out, flags, st);
@@ -314,6 +342,12 @@ hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, c
                         uint32_t* flags, hipStream_t st) {
   if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
   return write(nm, n, LeBlock{rows}, offs, out, flags, st);
+}
+
+hipError_t render_write(const RenderNames& nm, uint32_t n, const QuantRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
+  return write(nm, n, QuantileBlock{rows}, offs, out, flags, st);
 }
 
 }  // namespace l5dh

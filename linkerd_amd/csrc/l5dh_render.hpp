@@ -1,10 +1,11 @@
 // l5dh_render.hpp -- the Prometheus exposition of Stats, rendered on the device
-// (l5dh_render.hip): per row of a name table the summary block or the `_hist` block,
-// byte for byte what linkerd_amd/prometheus.py prints.
+// (l5dh_render.hip): per row of a name table the summary block, the `_hist` block or the
+// configured quantiles' block, byte for byte what linkerd_amd/prometheus.py prints.
 #pragma once
 
 #include "l5dh_kernels.hpp"
 #include "l5dh_le.hpp"
+#include "l5dh_quant.hpp"
 
 namespace l5dh {
 
@@ -43,6 +44,12 @@ struct LeRows {
   const int64_t* le;        // [K] the labels
   uint32_t K;
 };
+constexpr uint32_t RENDER_QLABEL_SLOT = 32;  // per quantile: its Double.toString (26 bytes at most), the length last
+struct QuantRows {
+  const int64_t* q_rows;  // [nvalues][K]
+  const uint8_t* labels;  // [K][RENDER_QLABEL_SLOT]: formatted once per call on the host
+  uint32_t K;
+};
 
 // Length pass: len[j] = bytes of row j's block for j < n (a row with a finding: 0, and its
 // flag word is lowered).  flags must hold 0xFFFFFFFF words.
@@ -50,11 +57,15 @@ hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, c
                           uint32_t* flags, hipStream_t st);
 hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const LeRows& rows, uint32_t* len,
                           uint32_t* flags, hipStream_t st);
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const QuantRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st);
 // Write pass: row j's block at out + offs[j] (offs: the exclusive prefix of len, offs[n] the
 // total).  Only launched when the length pass raised no flag: it trusts the table.
 hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
                         uint32_t* flags, hipStream_t st);
 hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st);
+hipError_t render_write(const RenderNames& nm, uint32_t n, const QuantRows& rows, const uint64_t* offs, uint8_t* out,
                         uint32_t* flags, hipStream_t st);
 
 }  // namespace l5dh

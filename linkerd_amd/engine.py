@@ -514,6 +514,64 @@ class HistogramEngine:
         self.le_counts_into(cuts, le, sums, dense=(counts, totals))
         return le, sums
 
+    # -- configurable quantiles ------------------------------------------------------
+    @staticmethod
+    def _q(q):
+        """The float64 quantiles of a call: a torch tensor as it is, anything else as a
+        numpy array (count and range are checked by the library)."""
+        if _is_torch(q):
+            return q
+        return np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1))
+
+    def quantiles_into(self, q, out, series=None, first: int = 0, count: Optional[int] = None,
+                       reset: bool = False, dense=None) -> None:
+        """Exact quantiles into caller buffers (numpy, or torch tensors on the engine's
+        GPU): out int64 [count][K] -- per series the value of each of the K quantiles
+        ``q`` (float64 in [0, 1], any order, duplicates legal; upstream
+        BucketedHistogram.percentile).  dense=None reads the live rows of series [first,
+        first+count) (l5dh_quantiles; ``series`` then receives the per-series summaries
+        of the same state and ``reset`` clears the range, atomically with the
+        quantiles); dense=counts reads external dense rows (l5dh_quantiles_dense)."""
+        if dense is not None:
+            n = _numel(dense) // N.NBUCKETS
+            if n * N.NBUCKETS != _numel(dense):
+                raise ValueError("dense counts must hold whole rows of 1798 buckets")
+            if series is not None or reset:
+                raise ValueError("dense rows have no series snapshot and nothing to reset")
+            first, count = 0, n
+        else:
+            first, count = self._range(first, count)
+        q = self._q(q)
+        K = _numel(q)
+        qp = self._buf(q, (np.float64,), "q")
+        op = self._buf(out, (np.int64,), "out", count * K, writable=True)
+        if out is None:
+            raise ValueError("out: an output buffer is needed")
+        if dense is not None:
+            dcp = self._buf(dense, (np.int32,), "dense counts")
+            self._check(self._lib.l5dh_quantiles_dense(self._ctx, dcp, count, qp, K, op), "l5dh_quantiles_dense")
+            return
+        rp = self._summ_buf(series, count, "series")
+        self._check(self._lib.l5dh_quantiles(self._ctx, first, count, qp, K, op, rp, int(reset)), "l5dh_quantiles")
+
+    def quantiles(self, q, first: int = 0, count: Optional[int] = None, reset: bool = False,
+                  with_series: bool = False):
+        """int64 [count][K]: the K quantiles ``q`` of series [first, first+count), followed
+        by the per-series summaries of the same state with ``with_series``; ``reset``
+        clears the range atomically with both."""
+        first, count = self._range(first, count)
+        out = np.zeros((count, _numel(self._q(q))), np.int64)
+        series = np.zeros(count, dtype=N.SUMMARY_DTYPE) if with_series else None
+        self.quantiles_into(q, out, series, first=first, count=count, reset=reset)
+        return (out, series) if with_series else out
+
+    def quantiles_dense(self, counts, q):
+        """The same over external dense rows (counts [n][1798] int32), e.g. the g_counts of
+        a rollup: the exact quantiles of the members' union."""
+        out = np.zeros((_numel(counts) // N.NBUCKETS, _numel(self._q(q))), np.int64)
+        self.quantiles_into(q, out, dense=counts)
+        return out
+
     # -- Prometheus text on the device ------------------------------------------------
     def _names(self, names) -> "N.Names":
         """The l5dh_names of a prometheus.NameTable (numpy arrays, or torch tensors on the
@@ -586,6 +644,23 @@ class HistogramEngine:
         nm, n = self._names(names), names.n
         return self._render(lambda op, cap, ln: self._lib.l5dh_render_le(
             self._ctx, ctypes.byref(nm), n, rp, sp, nvalues, lp, K, op, cap, ln), "l5dh_render_le", out)
+
+    def render_quantiles(self, names, q_rows, q, out=None):
+        """The configured quantiles' blocks (K lines ``key{..., quantile="<label>"} N``,
+        the label Java's Double.toString of the quantile) of the rows of ``names`` from
+        q_rows int64 [nvalues][K] and the K quantiles ``q`` (float64) -- what quantiles
+        returns and took.  Byte for byte prometheus.write_quantile_metrics' lines.
+        Returns as render_summaries does."""
+        q = self._q(q)
+        K = _numel(q)
+        qp = self._buf(q, (np.float64,), "q")
+        nvalues = _numel(q_rows) // K if K else 0  # (K = 0 is the library's to refuse)
+        if K and nvalues * K != _numel(q_rows):
+            raise ValueError("q_rows must hold whole rows of K values")
+        rp = self._buf(q_rows, (np.int64,), "q_rows")
+        nm, n = self._names(names), names.n
+        return self._render(lambda op, cap, ln: self._lib.l5dh_render_quantiles(
+            self._ctx, ctypes.byref(nm), n, rp, nvalues, qp, K, op, cap, ln), "l5dh_render_quantiles", out)
 
     # -- fleet merge (RCCL) ------------------------------------------------------
     @staticmethod

@@ -112,6 +112,25 @@ def write_histogram_metrics(tree: MetricsTree, engine, out: List[str], prefix0: 
         write_histogram_metrics(child, engine, out, prefix1 + (name,), labels1)
 
 
+def write_quantile_metrics(tree: MetricsTree, engine, out: List[str], prefix0: Tuple[str, ...] = (),
+                           labels0: Labels = ()) -> None:
+    """The configured quantiles of ``engine`` (a StatEngine after enable_quantiles) as
+    further lines of each Stat's summary: ``{key}{..., quantile="<label>"} <value>`` per
+    quantile, the label Java's Double.toString of it (0.75, 0.995, 1.0E-4), the value the
+    last snapshot_all_quantiles'.  A Stat prints them only if it holds a series id and has
+    a snapshotted summary -- beside the summary block write_metrics prints, never without
+    it.  Keys, labels and escaping are write_metrics'."""
+    prefix1, labels1 = _rewrite(prefix0, labels0)
+    m = tree.metric
+    if (isinstance(m, Metric.Stat) and m.series_id is not None and m.snapshotted_summary is not None
+            and engine.quantile_q is not None):
+        key = escape_key(":".join(prefix1))
+        for label, v in zip(engine.quantile_labels, engine.quantile_values[m.series_id]):
+            out.append(f"{key}{format_labels(labels1 + (('quantile', label),))} {long_to_string(int(v))}\n")
+    for name, child in tree.children.items():
+        write_quantile_metrics(child, engine, out, prefix1 + (name,), labels1)
+
+
 NO_INDEX = 0xFFFFFFFF  # NameTable.index of a Stat without a series id (no device call takes such a row)
 
 
@@ -237,7 +256,7 @@ class PrometheusTelemeter:
 
     path = "/admin/metrics/prometheus"
 
-    def __init__(self, metrics: MetricsTree, rollups=None, histograms=None):
+    def __init__(self, metrics: MetricsTree, rollups=None, histograms=None, quantiles=None):
         self.metrics = metrics
         # optional (RollupPlan, group summaries) pair of linkerd_amd.rollup, settable
         # later: its lines follow the tree's
@@ -245,6 +264,9 @@ class PrometheusTelemeter:
         # optional StatEngine with enable_le, settable later: the Stats' cumulative
         # `le` bucket lines (write_histogram_metrics) follow the tree's and the rollups'
         self.histograms = histograms
+        # optional StatEngine with enable_quantiles, settable later: the Stats' configured
+        # quantile lines (write_quantile_metrics) follow the `_hist` blocks
+        self.quantiles = quantiles
 
     def render(self) -> str:
         out: List[str] = []
@@ -255,13 +277,16 @@ class PrometheusTelemeter:
             write_rollup_metrics(plan, summaries, out)
         if self.histograms is not None:
             write_histogram_metrics(self.metrics, self.histograms, out)
+        if self.quantiles is not None:
+            write_quantile_metrics(self.metrics, self.quantiles, out)
         return "".join(out)
 
     def render_bytes(self, engine, names: "NameTable" = None, summaries=None) -> bytes:
         """The exposition as bytes, the Stats' text rendered on the device by ``engine``
         (a HistogramEngine): the counter and gauge lines (printed here: the engine does
         not hold them), the Stat blocks, the rollup blocks if ``rollups`` is set, the
-        ``_hist`` blocks if ``histograms`` is set.  As a line multiset this is render().
+        ``_hist`` blocks if ``histograms`` is set, the configured quantiles' blocks if
+        ``quantiles`` is set.  As a line multiset this is render().
         ``names``: stat_name_table(self.metrics) kept by the caller (host memory, or
         to_device() for the device calls); built here when None.  ``summaries``: the
         snapshot's records indexed by series id, host or device (every Stat of the table
@@ -302,6 +327,16 @@ class PrometheusTelemeter:
                 live = host.take([j for j, m in enumerate(host.metrics) if m.series_id is not None])
             if live.n:
                 parts.append(engine.render_le(live, h.le_buckets, h.le_sums, h.le_labels))
+        qe = self.quantiles
+        if qe is not None and qe.quantile_q is not None and table.n:
+            # write_quantile_metrics prints every Stat with a series id and a snapshotted summary
+            if host is None:
+                host = stat_name_table(self.metrics)
+            rows = [j for j, m in enumerate(host.metrics)
+                    if m.series_id is not None and m.snapshotted_summary is not None]
+            if rows:
+                shown = host if len(rows) == host.n else host.take(rows)
+                parts.append(engine.render_quantiles(shown, qe.quantile_values, qe.quantile_q))
         return b"".join(parts)
 
 

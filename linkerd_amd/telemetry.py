@@ -82,6 +82,10 @@ class StatEngine:
         self.le_labels: Optional[np.ndarray] = None
         self.le_buckets: Optional[np.ndarray] = None
         self.le_sums: Optional[np.ndarray] = None
+        # configured quantiles (enable_quantiles): the q, their labels, the last interval's values
+        self.quantile_q: Optional[np.ndarray] = None
+        self.quantile_labels: Optional[List[str]] = None
+        self.quantile_values: Optional[np.ndarray] = None
 
     # registry (MetricsTree.mkStat assigns the id; MetricsTree.prune releases it)
     def register(self) -> int:
@@ -103,6 +107,8 @@ class StatEngine:
         if self.le_cuts is not None:  # the id's lifetime buckets end with its Stat
             self.le_buckets[sid] = 0
             self.le_sums[sid] = 0
+        if self.quantile_q is not None:
+            self.quantile_values[sid] = 0
         with self._lock:
             self._free.append(sid)
 
@@ -117,9 +123,9 @@ class StatEngine:
         interval of this one (its rows leave with export_sparse(reset=True) and enter with
         import_sparse, so they cost what the data costs, not 7192 B per series), the ids
         held by Stats stay valid, and register() succeeds again.  The lifetime ``le``
-        counters are kept and extended with zero rows.  Adds from other threads wait for the
-        swap; snapshot calls must not run beside it.  Tunables set on the old engine
-        (HistogramEngine.set_param) are not carried over."""
+        counters and the last interval's quantile values are kept and extended with zero
+        rows.  Adds from other threads wait for the swap; snapshot calls must not run beside
+        it.  Tunables set on the old engine (HistogramEngine.set_param) are not carried over."""
         capacity = int(capacity)
         self.flush()
         with self._lock:
@@ -145,6 +151,10 @@ class StatEngine:
                     more = self.capacity - self.le_buckets.shape[0]
                     self.le_buckets = np.concatenate([self.le_buckets, np.zeros((more, K1), np.uint64)])
                     self.le_sums = np.concatenate([self.le_sums, np.zeros(more, np.int64)])
+                if self.quantile_q is not None:
+                    more = self.capacity - self.quantile_values.shape[0]
+                    self.quantile_values = np.concatenate(
+                        [self.quantile_values, np.zeros((more, self.quantile_q.size), np.int64)])
                 old.close()
             finally:
                 for st in bufs:
@@ -153,14 +163,17 @@ class StatEngine:
     def checkpoint(self, reset: bool = False) -> Dict[str, np.ndarray]:
         """The open interval and the registry as numpy arrays (np.savez takes the dict as it
         is): the sparse rows and totals of every id handed out so far, the next id, the
-        free list, and the ``le`` cuts, labels and lifetime counters.  ``reset`` ends the
-        interval here (what a process does before it stops)."""
+        free list, the ``le`` cuts, labels and lifetime counters, and the configured
+        quantiles with the last interval's values (``quantile_q`` is empty when
+        enable_quantiles was not called).  ``reset`` ends the interval here (what a process
+        does before it stops)."""
         self.flush()
         with self._lock:
             n = self._next
             row_off, entries, totals = self.engine.export_sparse(first=0, count=n, reset=reset)
             le = self.le_cuts is not None
             K1 = self.le_buckets.shape[1] if le else 1
+            qt = self.quantile_q is not None
             return {
                 "row_off": row_off, "entries": entries, "totals": totals,
                 "next": np.array([n], np.int64), "free": np.array(self._free, np.uint32),
@@ -168,12 +181,15 @@ class StatEngine:
                 "le_labels": self.le_labels.copy() if le else np.zeros(0, np.int64),
                 "le_buckets": self.le_buckets[:n].copy() if le else np.zeros((0, K1), np.uint64),
                 "le_sums": self.le_sums[:n].copy() if le else np.zeros(0, np.int64),
+                "quantile_q": self.quantile_q.copy() if qt else np.zeros(0, np.float64),
+                "quantile_values": self.quantile_values[:n].copy() if qt else np.zeros((0, 0), np.int64),
             }
 
     def restore(self, ckpt) -> None:
         """Take over a checkpoint: on a fresh StatEngine (no id handed out yet) of at least
         the checkpoint's ids.  Afterwards the engine reports what the checkpointed one
-        did, and register() continues where it stopped."""
+        did, and register() continues where it stopped.  A checkpoint written before the
+        configured quantiles existed (no ``quantile_q``) restores with them off."""
         from . import _native as N
         n = int(np.asarray(ckpt["next"]).reshape(-1)[0])
         with self._lock:
@@ -196,6 +212,10 @@ class StatEngine:
                 self.le_sums = np.zeros(self.capacity, np.int64)
                 self.le_buckets[:n] = np.asarray(ckpt["le_buckets"], np.uint64).reshape(n, cuts.size + 1)
                 self.le_sums[:n] = np.asarray(ckpt["le_sums"], np.int64).reshape(-1)
+            qs = np.asarray(ckpt["quantile_q"], np.float64).reshape(-1) if "quantile_q" in ckpt else np.zeros(0)
+            if qs.size:
+                self.enable_quantiles(qs)
+                self.quantile_values[:n] = np.asarray(ckpt["quantile_values"], np.int64).reshape(n, qs.size)
 
     def _staging(self) -> "_Staging":
         st = getattr(self._tls, "st", None)
@@ -291,6 +311,59 @@ class StatEngine:
             return self.engine.snapshot(first=0, count=self.capacity, reset=False)
         return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True, with_series=True,
                                      accumulate_into=(self.le_buckets, self.le_sums))[2]
+
+    # configurable quantiles (any q, beside the summary's six)
+    def enable_quantiles(self, qs) -> None:
+        """Report the exact quantiles ``qs`` of every series per interval: quantile_q
+        (float64, ascending), quantile_labels (their Java Double.toString, the
+        exposition's ``quantile`` label) and quantile_values int64 [capacity][K], written
+        by snapshot_all_quantiles.  1..64 distinct values in [0, 1], none of the eight the
+        summary block prints already (0, 0.5, 0.9, 0.95, 0.99, 0.999, 0.9999, 1): those
+        would duplicate a series of the exposition.  Calling it again starts anew."""
+        from .javafmt import double_to_string
+        q = np.sort(np.asarray(qs, np.float64).reshape(-1))
+        if not 1 <= q.size <= 64:
+            raise ValueError(f"enable_quantiles: {q.size} quantiles, 1..64 are supported")
+        if not np.all((q >= 0.0) & (q <= 1.0)):  # (NaN fails both)
+            raise ValueError("enable_quantiles: every quantile must be in [0, 1]")
+        if np.unique(q).size != q.size:
+            raise ValueError("enable_quantiles: duplicate quantiles")
+        taken = sorted(set(q.tolist()) & {0.0, 0.5, 0.9, 0.95, 0.99, 0.999, 0.9999, 1.0})
+        if taken:
+            raise ValueError(f"enable_quantiles: {taken} are quantiles of the summary block already")
+        self.quantile_q = q
+        self.quantile_labels = [double_to_string(float(x)) for x in q]
+        self.quantile_values = np.zeros((self.capacity, q.size), np.int64)
+
+    def snapshot_all_quantiles(self, reset: bool = True) -> np.ndarray:
+        """snapshot_all plus the interval's configured quantiles, which overwrite
+        quantile_values (quantiles do not accumulate).  With enable_le on, the same call
+        also feeds the lifetime ``le`` counters: every staging lock is held (as grow holds
+        them) over the two engine calls -- quantiles(reset=False), then
+        le_counts(reset=True, with_series=True) -- so no add can fall between them and
+        both see exactly the same samples.  reset=False only looks and leaves the ``le``
+        counters alone, as snapshot_all_le does."""
+        if self.quantile_q is None:
+            raise RuntimeError("snapshot_all_quantiles needs enable_quantiles(qs) first")
+        if not reset or self.le_cuts is None:
+            self.flush()
+            self.quantile_values, summaries = self.engine.quantiles(
+                self.quantile_q, first=0, count=self.capacity, reset=reset, with_series=True)
+            return summaries
+        with self._lock:  # (held throughout: a thread's first add, which registers its batch, waits too)
+            bufs = list(self._buffers)
+            for st in bufs:
+                st.lock.acquire()
+            try:
+                for st in bufs:
+                    self._flush_locked(st)
+                self.quantile_values = self.engine.quantiles(self.quantile_q, first=0, count=self.capacity,
+                                                             reset=False)
+                return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True,
+                                             with_series=True, accumulate_into=(self.le_buckets, self.le_sums))[2]
+            finally:
+                for st in bufs:
+                    st.lock.release()
 
 
 class _Staging:
@@ -555,6 +628,21 @@ def snapshot_histograms_le(tree: MetricsTree, engine: StatEngine) -> int:
     (StatEngine.enable_le) by the same engine call.  Returns the number of Stats updated."""
     now = time.time()
     summaries = engine.snapshot_all_le(reset=True)
+    n = 0
+    for _, t in tree.walk():
+        m = t.metric
+        if isinstance(m, Metric.Stat) and m.series_id is not None:
+            m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
+            n += 1
+    return n
+
+
+def snapshot_histograms_quantiles(tree: MetricsTree, engine: StatEngine) -> int:
+    """snapshot_histograms plus the configured quantiles (StatEngine.enable_quantiles) of
+    the same interval -- and, with enable_le, the lifetime `le` counters fed by it.  Returns
+    the number of Stats updated."""
+    now = time.time()
+    summaries = engine.snapshot_all_quantiles(reset=True)
     n = 0
     for _, t in tree.walk():
         m = t.metric
