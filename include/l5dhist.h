@@ -286,6 +286,65 @@ int l5dh_quantiles(l5dh_ctx* ctx, uint32_t first, uint32_t count, const double* 
 int l5dh_quantiles_dense(l5dh_ctx* ctx, const int32_t* counts, size_t n, const double* q, uint32_t nq,
                          int64_t* q_out /* [n][nq] */);
 
+/* Exact top-k: WHICH series are the worst -- the k rows with the largest (or smallest) value
+ * of one summary field, or of any quantile, selected where the numbers are: a full engine's
+ * summaries never leave the device, k ids and k summaries do.
+ *
+ * Candidates: row i is a candidate iff its count >= min_count and (group == NULL or group[i]
+ * == g).  Every other map value, L5DH_NO_GROUP included, means "not a member" -- nothing about
+ * the map is an error, so the group map of a rollup can be passed as it is.  min_count = 0
+ * admits empty rows (a live series of a clean tile has the all-zero summary).
+ * Key: `by` names the field by its index in l5dh_summary; fields 0..9 compare as signed int64,
+ * avg in the IEEE total order of its bits (-NaN < -Inf < ... < -0.0 < +0.0 < ... < +Inf < +NaN:
+ * external garbage still has one answer).  L5DH_BY_QUANTILE (live state only) ranks by
+ * BucketedHistogram.percentile(q) of the row, exactly what l5dh_quantiles returns for that q.
+ * Order: by key descending (L5DH_TOP_LARGEST) or ascending (L5DH_TOP_SMALLEST); equal keys by
+ * ascending id in both.  The id is first + i for the live call, the row index i for the
+ * external one.  *n_out = min(k, number of candidates); ids_out[0 .. *n_out), top_out[0 ..
+ * *n_out) (the winners' whole summaries) and q_out[0 .. *n_out) (their quantile values; by ==
+ * L5DH_BY_QUANTILE only, ignored otherwise) are written and nothing beyond them.  The answer is
+ * a pure function of the inputs: the same on every run, for host and for device pointers.
+ *
+ * l5dh_top: live state.  Under ONE hold of the context lock: staged samples are binned and
+ * pending segments folded; for L5DH_BY_QUANTILE the quantile of every series of the range is
+ * taken; the per-series snapshot of [first, first + count) is taken from the same state
+ * (series_out: count l5dh_summary, nullable) and, with reset != 0, the range is cleared; the
+ * selection then runs over those summaries or quantile values -- the ranking, series_out and
+ * the reset all see exactly the same samples.
+ * l5dh_top_summaries: external summaries values[n] (e.g. the g_out of a rollup: "the worst
+ * routers").  Reads no engine state: it holds the context lock only to use its stream and
+ * scratch.
+ * Every pointer may be host or device memory.  count == 0 (n == 0) sets *n_out = 0.
+ * -EINVAL, found on the host before anything is enqueued, with nothing written and nothing
+ * reset: k outside [1, L5DH_TOP_LIMIT]; `by` outside the enum, or L5DH_BY_QUANTILE in
+ * l5dh_top_summaries; order not 0 or 1; min_count < 0; q NaN or outside [0, 1] with
+ * L5DH_BY_QUANTILE (q is ignored otherwise); a bad range; n > 2^24; a null ids_out or n_out;
+ * a null values with n > 0. */
+#define L5DH_TOP_LIMIT 1024 /* k per call */
+enum {
+  L5DH_BY_COUNT = 0,
+  L5DH_BY_MIN = 1,
+  L5DH_BY_MAX = 2,
+  L5DH_BY_SUM = 3,
+  L5DH_BY_P50 = 4,
+  L5DH_BY_P90 = 5,
+  L5DH_BY_P95 = 6,
+  L5DH_BY_P99 = 7,
+  L5DH_BY_P9990 = 8,
+  L5DH_BY_P9999 = 9,
+  L5DH_BY_AVG = 10,     /* = the field's index in l5dh_summary */
+  L5DH_BY_QUANTILE = 11 /* live state only: percentile(q) */
+};
+enum { L5DH_TOP_LARGEST = 0, L5DH_TOP_SMALLEST = 1 };
+int l5dh_top(l5dh_ctx* ctx, uint32_t first, uint32_t count, int by, double q, int order, int64_t min_count,
+             const uint32_t* group /* [count], nullable */, uint32_t g, uint32_t k,
+             uint32_t* ids_out /* [k] */, l5dh_summary* top_out /* [k], nullable */,
+             int64_t* q_out /* [k], nullable; by == QUANTILE */, uint32_t* n_out,
+             l5dh_summary* series_out /* [count], nullable */, int reset);
+int l5dh_top_summaries(l5dh_ctx* ctx, const l5dh_summary* values, size_t n, int by, int order, int64_t min_count,
+                       const uint32_t* group /* [n], nullable */, uint32_t g, uint32_t k,
+                       uint32_t* ids_out, l5dh_summary* top_out /* nullable */, uint32_t* n_out);
+
 /* State import and sparse export: the way INTO the bucket rows, and the CSR form of the way
  * out.  Rows that left an engine -- l5dh_export_state / l5dh_export_sparse output, the slice
  * of a merge, the g_counts of a rollup, the non-empty buckets of a peek -- enter another one:

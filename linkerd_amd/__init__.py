@@ -11,6 +11,7 @@ Modules:
   engine     HistogramEngine (one context = one GPU shard)
   telemetry  MetricsTree / Metric.{Counter,Stat,Gauge} / HistogramSummary mirror
   prometheus PrometheusTelemeter text export from GPU summaries
+  top        /admin/metrics/top.json: the exact top-k Stats, selected on the GPU
   fleet      multi-GPU series sharding and the RCCL fleet merge
   synth      synthetic workloads C1-C4 of BASELINE.md
 """

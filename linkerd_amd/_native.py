@@ -47,6 +47,14 @@ Q_MAX = 64  # L5DH_Q_MAX
 DOUBLE_CHARS = 26  # L5DH_DOUBLE_CHARS
 LONG_CHARS = 20  # L5DH_LONG_CHARS
 
+# top-k selection (l5dh_top, l5dh_top_summaries; the kernels' constants: csrc/l5dh_top.hpp)
+TOP_LIMIT = 1024  # L5DH_TOP_LIMIT: k per call
+TOP_CHUNK = 4096  # rows one workgroup of the tournament sorts
+TOP_MAX_ROWS = 1 << 24  # rows of one external selection
+(BY_COUNT, BY_MIN, BY_MAX, BY_SUM, BY_P50, BY_P90, BY_P95, BY_P99, BY_P9990, BY_P9999, BY_AVG,
+ BY_QUANTILE) = range(12)  # L5DH_BY_*: the field's index in SUMMARY_FIELDS; BY_QUANTILE: percentile(q), live only
+TOP_LARGEST, TOP_SMALLEST = 0, 1  # L5DH_TOP_*
+
 
 class Names(ctypes.Structure):
     """l5dh_names: the five arrays of a name table (host or device addresses; 0: NULL)."""
@@ -97,6 +105,10 @@ SIGNATURES = {
     "l5dh_le_dense": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
     "l5dh_quantiles": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp, _vp, _c.c_int]),
     "l5dh_quantiles_dense": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp]),
+    "l5dh_top": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_double, _c.c_int, _c.c_int64, _vp, _c.c_uint32,
+                            _c.c_uint32, _vp, _vp, _vp, _vp, _vp, _c.c_int]),
+    "l5dh_top_summaries": (_c.c_int, [_vp, _vp, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int64, _vp, _c.c_uint32,
+                                      _c.c_uint32, _vp, _vp, _vp]),
     "l5dh_import_state": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp]),
     "l5dh_export_sparse": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_size_t, _c.POINTER(_c.c_size_t),
                                       _vp, _c.c_int]),

@@ -20,6 +20,7 @@
 #include "l5dh_quant.hpp"
 #include "l5dh_render.hpp"
 #include "l5dh_rollup.hpp"
+#include "l5dh_top.hpp"
 
 namespace l5dh {
 
@@ -145,6 +146,9 @@ struct l5dh_ctx {
   DevBuf le_stage, le_sums_stage;  // cumulative `le` buckets (l5dh_le.hip): staged outputs
   DevBuf q_stage;                  // configurable quantiles (l5dh_quant.hip): staged output
   DevBuf rd_qlabels;               // the device renderer's quantile labels, formatted on the host
+  // top-k selection (l5dh_top.hip): staged external rows and group map, the K = 1 quantile values,
+  // the two list buffers of the tournament, staged outputs (ids, summaries, quantile values), the count
+  DevBuf top_vals, top_group, top_q, top_list_a, top_list_b, top_ids, top_summ, top_qout, top_n;
   // state import and sparse export (l5dh_import.hip): status words, staged CSR inputs, the clean
   // tiles' flags and list; the export's row counts, offsets, scan scratch and staged entries
   DevBuf imp_status, imp_series, imp_off, imp_entries, imp_tflag, imp_list;

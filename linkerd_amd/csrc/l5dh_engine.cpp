@@ -651,6 +651,119 @@ int do_quant(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, co
   return sync_stream(c);
 }
 
+// ---- top-k selection ------------------------------------------------------------------
+// What to rank by and whom: the checked arguments the two entry points share.
+struct TopQuery {
+  int by;             // 0 .. 10: the summary field; L5DH_BY_QUANTILE: percentile(q) of the live row
+  double q;
+  int order;          // L5DH_TOP_LARGEST / L5DH_TOP_SMALLEST
+  int64_t min_count;
+  const uint32_t* group;  // nullable
+  uint32_t g, k;
+};
+
+// -EINVAL for everything a selection can be asked wrongly, before anything is enqueued.
+// by_max: the largest `by` the entry point takes.
+int top_check(l5dh_ctx* c, const TopQuery& t, int by_max, const void* ids_out, const void* n_out) {
+  if (t.k < 1 || t.k > L5DH_TOP_LIMIT) return fail(c, -EINVAL, "top: k must be in [1, 1024]");
+  if (t.by < 0 || t.by > by_max) return fail(c, -EINVAL, "top: unknown `by` for this call");
+  if (t.order != L5DH_TOP_LARGEST && t.order != L5DH_TOP_SMALLEST) return fail(c, -EINVAL, "top: order must be 0 or 1");
+  if (t.min_count < 0) return fail(c, -EINVAL, "top: min_count must be >= 0");
+  if (t.by == L5DH_BY_QUANTILE && !(t.q >= 0.0 && t.q <= 1.0)) return fail(c, -EINVAL, "top: q is not in [0, 1]");
+  if (!ids_out || !n_out) return fail(c, -EINVAL, "top: null ids_out or n_out");
+  return 0;
+}
+
+// A u32 to the caller's host or device word.
+int top_put_n(l5dh_ctx* c, uint32_t* n_out, uint32_t v) {
+  if (!is_device_ptr(n_out)) {
+    *n_out = v;
+    return 0;
+  }
+  HIPCHK(c, hipMemcpyAsync(n_out, &v, 4, hipMemcpyHostToDevice, c->stream));
+  return sync_stream(c);
+}
+
+// The k best of `count` rows: the live state rows of series [first, first + count) (ext ==
+// nullptr; then also the K = 1 quantile pass, the per-series snapshot and the reset of the
+// same state) or external summaries ext[count] (first == 0).  The caller holds the lock and
+// has checked the arguments; 0 < count <= TOP_MAX_ROWS.
+int do_top(l5dh_ctx* c, uint32_t first, uint32_t count, const Summary88* ext, const TopQuery& t, uint32_t* ids_out,
+           l5dh_summary* top_out, int64_t* q_out, uint32_t* n_out, l5dh_summary* series_out, int reset) {
+  int r;
+  const bool live = ext == nullptr;
+  const bool byq = t.by == L5DH_BY_QUANTILE;
+  const uint32_t kp = top_kp(t.k);
+  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
+  StagedOut<Summary88> s_summ, top;
+  StagedOut<uint32_t> ids;
+  StagedOut<int64_t> qo;
+  const uint32_t* group = t.group;
+  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_quantiles)
+  if ((r = stage_in(c, ext, count, 8, c->top_vals)) || (r = stage_in(c, group, count, 4, c->top_group)) ||
+      (r = ensure(c, c->top_list_a, top_bytes_a(count, kp))) || (r = ensure(c, c->top_list_b, top_bytes_b(count, kp))) ||
+      (r = ensure(c, c->top_n, 4)) || (r = ids.begin(c, ids_out, t.k, c->top_ids, 4)) ||
+      (r = top.begin(c, top_out, t.k, c->top_summ)) || (r = qo.begin(c, byq ? q_out : nullptr, t.k, c->top_qout)))
+    return r;
+  // the rows ranked: the external ones, or the live range's summaries in series_out's
+  // (staged) buffer, or in the same staging buffer as scratch
+  Summary88* live_rows = nullptr;
+  if (live) {
+    if ((r = s_summ.begin(c, series_out, count, c->stage_summ))) return r;
+    live_rows = s_summ.dev;
+    if (!live_rows) {
+      if ((r = ensure(c, c->stage_summ, (size_t)count * sizeof(Summary88)))) return r;
+      live_rows = c->stage_summ.as<Summary88>();
+    }
+    if (byq && (r = ensure(c, c->top_q, (size_t)count * 8))) return r;
+  }
+  TopArgs a{};
+  a.summ = live ? live_rows : ext;
+  a.qv = byq ? c->top_q.as<const int64_t>() : nullptr;
+  a.group = group;
+  a.g = t.g;
+  a.n = count;
+  a.first = first;
+  a.by = (uint32_t)t.by;
+  a.smallest = t.order == L5DH_TOP_SMALLEST;
+  a.min_count = t.min_count;
+  a.k = t.k;
+  a.list_a = c->top_list_a.as<TopItem>();
+  a.list_b = c->top_list_b.as<TopItem>();
+  a.ids_out = ids.dev;
+  a.top_out = top.dev;
+  a.q_out = qo.dev;
+  a.n_out = c->top_n.as<uint32_t>();
+  a.n_out2 = is_device_ptr(n_out) ? n_out : nullptr;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    if (live) {
+      if (byq) {  // the existing kernel with K = 1, before any reset
+        QuantQ qs;
+        memset(&qs, 0, sizeof(qs));
+        qs.q[0] = t.q;
+        HIPCHK(c, launch_quant(state(c), first, count, nullptr, qs, 1, tables(c).mid, c->top_q.as<int64_t>(), c->stream));
+      }
+      // the per-series summaries and the reset of the same range, from the same state
+      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{live_rows, nullptr, first, count, nullptr},
+                            reset, nullptr, c->stream));
+    }
+    HIPCHK(c, launch_top(a, c->stream));
+  }
+  // the number of winners: what the host copies back of staged outputs, and no more
+  uint32_t m = 0;
+  HIPCHK(c, hipMemcpyAsync(&m, a.n_out, 4, hipMemcpyDeviceToHost, c->stream));
+  if ((r = sync_stream(c))) return r;
+  if (m > t.k) return fail(c, -EIO, "internal: top-k count out of range");
+  if (!a.n_out2) *n_out = m;
+  if (m && ids.staged()) HIPCHK(c, hipMemcpyAsync(ids.user, ids.dev, (size_t)m * 4, hipMemcpyDefault, c->stream));
+  if (m && top.staged())
+    HIPCHK(c, hipMemcpyAsync(top.user, top.dev, (size_t)m * sizeof(Summary88), hipMemcpyDefault, c->stream));
+  if (m && qo.staged()) HIPCHK(c, hipMemcpyAsync(qo.user, qo.dev, (size_t)m * 8, hipMemcpyDefault, c->stream));
+  if ((r = s_summ.end(c))) return r;
+  return sync_stream(c);
+}
+
 // ---- state import and sparse export -------------------------------------------------
 // The status words of an import, read in one copy and one wait.
 int imp_read_status(l5dh_ctx* c, uint32_t (&hs)[IS_WORDS]) {
@@ -1139,6 +1252,35 @@ int l5dh_quantiles_dense(l5dh_ctx* c, const int32_t* counts, size_t n, const dou
   if (n == 0) return 0;
   if (!counts || !q_out) return fail(c, -EINVAL, "quantiles: null dense rows or output");
   return do_quant(c, 0, (uint32_t)n, counts, qs, nq, q_out, nullptr, 0);
+}
+
+int l5dh_top(l5dh_ctx* c, uint32_t first, uint32_t count, int by, double q, int order, int64_t min_count,
+             const uint32_t* group, uint32_t g, uint32_t k, uint32_t* ids_out, l5dh_summary* top_out, int64_t* q_out,
+             uint32_t* n_out, l5dh_summary* series_out, int reset) {
+  if (!c) return -EINVAL;
+  CtxLock lk(c);
+  static_assert(L5DH_TOP_LIMIT == TOP_LIMIT && L5DH_BY_QUANTILE == TOP_BY_QUANTILE && L5DH_BY_AVG == TOP_BY_FIELDS - 1,
+                "the header's constants are the kernels'");
+  const TopQuery t{by, q, order, min_count, group, g, k};
+  if (int r = top_check(c, t, L5DH_BY_QUANTILE, ids_out, n_out)) return r;
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (count == 0) return top_put_n(c, n_out, 0);
+  return do_top(c, first, count, nullptr, t, ids_out, top_out, q_out, n_out, series_out, reset);
+}
+
+int l5dh_top_summaries(l5dh_ctx* c, const l5dh_summary* values, size_t n, int by, int order, int64_t min_count,
+                       const uint32_t* group, uint32_t g, uint32_t k, uint32_t* ids_out, l5dh_summary* top_out,
+                       uint32_t* n_out) {
+  if (!c) return -EINVAL;
+  CtxLock lk(c);
+  const TopQuery t{by, 0.0, order, min_count, group, g, k};
+  if (int r = top_check(c, t, L5DH_BY_AVG, ids_out, n_out)) return r;
+  if (n > TOP_MAX_ROWS) return fail(c, -EINVAL, "top: more than 2^24 rows");
+  if (n == 0) return top_put_n(c, n_out, 0);
+  if (!values) return fail(c, -EINVAL, "top: null values");
+  static_assert(sizeof(l5dh_summary) == sizeof(Summary88), "l5dh_summary layout");
+  return do_top(c, 0, (uint32_t)n, reinterpret_cast<const Summary88*>(values), t, ids_out, top_out, nullptr, n_out,
+                nullptr, 0);
 }
 
 int l5dh_import_state(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {

@@ -572,6 +572,131 @@ class HistogramEngine:
         self.quantiles_into(q, out, dense=counts)
         return out
 
+    # -- exact top-k ------------------------------------------------------------------
+    @staticmethod
+    def _top_by(by, allow_quantile: bool = True):
+        """(by, q) of a ranking: a field name of SUMMARY_FIELDS, or a float q in [0, 1] for
+        BucketedHistogram.percentile(q) (live state only)."""
+        if isinstance(by, str):
+            if by not in N.SUMMARY_FIELDS:
+                raise ValueError(f"by: {by!r} is not one of {N.SUMMARY_FIELDS} (or a float quantile)")
+            return N.SUMMARY_FIELDS.index(by), 0.0
+        if isinstance(by, (float, np.floating)) or (isinstance(by, (int, np.integer)) and not isinstance(by, bool)):
+            if not allow_quantile:
+                raise ValueError("by: external summaries rank by a field name only (they hold no buckets)")
+            return N.BY_QUANTILE, float(by)
+        raise ValueError(f"by: {by!r} is neither a field name nor a float quantile")
+
+    @staticmethod
+    def _top_order(order) -> int:
+        try:
+            return {"largest": N.TOP_LARGEST, "smallest": N.TOP_SMALLEST}[order]
+        except (KeyError, TypeError):
+            raise ValueError(f"order: {order!r} is not 'largest' or 'smallest'") from None
+
+    def _top_group(self, group, rows: int):
+        """The uint32 member map of a ranking (None: every row): any value but ``g`` means
+        "not a member".  A numpy int32 / int64 map is converted, -1 standing for NO_GROUP."""
+        if group is None:
+            return None
+        if isinstance(group, np.ndarray):
+            if group.dtype in (np.dtype(np.int32), np.dtype(np.int64)):
+                if group.size and (group.min() < -1 or group.max() > N.NO_GROUP):
+                    raise ValueError("group: entries must be -1 (no group) or fit uint32")
+                group = np.where(group == -1, N.NO_GROUP, group).astype(np.uint32)
+            elif group.dtype != np.dtype(np.uint32):
+                raise ValueError(f"group: dtype {group.dtype} is not uint32 (or int32 / int64 with -1 for no group)")
+            group = np.ascontiguousarray(group)
+        elif not _is_torch(group):
+            raise ValueError(f"group: unsupported map type {type(group)!r}")
+        if _numel(group) != rows:
+            raise ValueError(f"group: {_numel(group)} entries for {rows} rows")
+        return group
+
+    def top_into(self, k: int, by, ids, n_out, summaries=None, q_values=None, order: str = "largest",
+                 min_count: int = 1, group=None, g: int = 0, first: int = 0, count: Optional[int] = None,
+                 reset: bool = False, series=None, values=None) -> None:
+        """The exact top ``k`` into caller buffers (numpy, or torch tensors on the engine's
+        GPU): ids uint32 [k], n_out uint32 [1] (= min(k, candidates)), summaries int64
+        [k*11] (or the numpy summary dtype: the winners' whole summaries), q_values int64
+        [k] (``by`` a float q).  Only the first n_out entries of each are written.
+        values=None ranks the live rows of series [first, first+count) (l5dh_top; ``series``
+        then receives the per-series summaries of the same state and ``reset`` clears the
+        range, atomically with the ranking); values=<summaries> ranks external summaries
+        (l5dh_top_summaries: numpy summary dtype, or int64 [n*11]), ids being row indices.
+        A row is a candidate iff its count >= min_count and (group is None or group[i] == g)."""
+        k = int(k)
+        if k < 1 or k > N.TOP_LIMIT:
+            raise ValueError(f"k must be in [1, {N.TOP_LIMIT}], got {k}")
+        by_i, q = self._top_by(by, allow_quantile=values is None)
+        order_i = self._top_order(order)
+        if values is not None:
+            if series is not None or reset:
+                raise ValueError("external summaries have no series snapshot and nothing to reset")
+            if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
+                rows = int(values.size)
+            else:
+                rows = _numel(values) // 11
+                if rows * 11 != _numel(values):
+                    raise ValueError("values must hold whole summaries of 11 words")
+            first, count = 0, rows
+        else:
+            first, count = self._range(first, count)
+        group = self._top_group(group, count)
+        gp = self._buf(group, (np.uint32, np.int32), "group", count)  # (a torch int32 map: the same words)
+        ip = self._buf(ids, (np.uint32, np.int32), "ids", k, writable=True)
+        np_ = self._buf(n_out, (np.uint32, np.int32), "n_out", 1, writable=True)
+        if ids is None or n_out is None:
+            raise ValueError("ids and n_out: output buffers are needed")
+        sp = self._summ_buf(summaries, k, "summaries")
+        if values is not None:
+            if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
+                if not values.flags["C_CONTIGUOUS"]:
+                    raise ValueError("values: array must be C-contiguous")
+                vp = values.ctypes.data if count else None
+            else:
+                vp = self._buf(values, (np.int64,), "values", count * 11) if count else None
+            self._check(self._lib.l5dh_top_summaries(self._ctx, vp, count, by_i, order_i, int(min_count), gp, int(g), k,
+                                                     ip, sp, np_), "l5dh_top_summaries")
+            return
+        qp = self._buf(q_values, (np.int64,), "q_values", k, writable=True)
+        rp = self._summ_buf(series, count, "series")
+        self._check(self._lib.l5dh_top(self._ctx, first, count, by_i, q, order_i, int(min_count), gp, int(g), k, ip, sp, qp,
+                                       np_, rp, int(reset)), "l5dh_top")
+
+    def top(self, k: int, by="p99", order: str = "largest", min_count: int = 1, group=None, g: int = 0,
+            first: int = 0, count: Optional[int] = None, reset: bool = False, with_series: bool = False):
+        """(ids uint32 [n], summaries [n]) of the ``k`` series of [first, first+count) with
+        the largest (``order="smallest"``: smallest) ``by`` -- a field name of
+        SUMMARY_FIELDS, or a float q for the exact q-quantile, whose values then follow as
+        int64 [n] -- in rank order, equal keys by ascending id; n = min(k, candidates).  The
+        per-series summaries of the same state follow with ``with_series``; ``reset`` clears
+        the range atomically with the ranking."""
+        first, count = self._range(first, count)
+        k = int(k)
+        by_q = self._top_by(by)[0] == N.BY_QUANTILE
+        kk = max(1, min(k, N.TOP_LIMIT))  # (an illegal k is reported by top_into)
+        ids, n_out = np.zeros(kk, np.uint32), np.zeros(1, np.uint32)
+        summ = np.zeros(kk, dtype=N.SUMMARY_DTYPE)
+        qv = np.zeros(kk, np.int64) if by_q else None
+        series = np.zeros(count, dtype=N.SUMMARY_DTYPE) if with_series else None
+        self.top_into(k, by, ids, n_out, summ, qv, order=order, min_count=min_count, group=group, g=g, first=first,
+                      count=count, reset=reset, series=series)
+        n = int(n_out[0])
+        return (ids[:n], summ[:n]) + ((qv[:n],) if by_q else ()) + ((series,) if with_series else ())
+
+    def top_summaries(self, values, k: int, by="p99", order: str = "largest", min_count: int = 1, group=None,
+                      g: int = 0):
+        """(row indices uint32 [n], summaries [n]) of the ``k`` best rows of external
+        summaries (numpy summary dtype or int64 [n*11]; a torch tensor on the engine's GPU is
+        read in place), e.g. the group summaries of a rollup: "the worst routers"."""
+        kk = max(1, min(int(k), N.TOP_LIMIT))
+        ids, n_out = np.zeros(kk, np.uint32), np.zeros(1, np.uint32)
+        summ = np.zeros(kk, dtype=N.SUMMARY_DTYPE)
+        self.top_into(k, by, ids, n_out, summ, order=order, min_count=min_count, group=group, g=g, values=values)
+        n = int(n_out[0])
+        return ids[:n], summ[:n]
+
     # -- Prometheus text on the device ------------------------------------------------
     def _names(self, names) -> "N.Names":
         """The l5dh_names of a prometheus.NameTable (numpy arrays, or torch tensors on the

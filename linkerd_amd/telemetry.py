@@ -286,6 +286,15 @@ class StatEngine:
                                             with_series=True)
         return series, groups
 
+    # exact top-k of the open interval
+    def top(self, k: int, by="p99", order: str = "largest", min_count: int = 1, group=None, g: int = 0):
+        """HistogramEngine.top over the whole capacity after flushing every thread's staged
+        adds; nothing is reset.  Released ids have zero rows, so with min_count >= 1 they
+        never rank."""
+        self.flush()
+        return self.engine.top(k, by, order=order, min_count=min_count, group=group, g=g, first=0,
+                               count=self.capacity, reset=False)
+
     # cumulative `le` buckets (Prometheus histogram counters)
     def enable_le(self, bounds) -> None:
         """Keep lifetime cumulative bucket counters at ``bounds`` (snapped down to exact
@@ -650,3 +659,38 @@ def snapshot_histograms_quantiles(tree: MetricsTree, engine: StatEngine) -> int:
             m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
             n += 1
     return n
+
+
+def top_stats(tree: MetricsTree, engine: StatEngine, k: int, by="p99", order: str = "largest", min_count: int = 1,
+              scope: Sequence[str] = ()) -> list:
+    """The ``k`` Stats of the open interval with the largest (``order="smallest"``:
+    smallest) ``by`` -- a HistogramSummary field name, or a float q for the exact
+    q-quantile -- as (path tuple, HistogramSummary[, q value]) in rank order.  The
+    selection runs on the GPU (StatEngine.top); nothing is reset and no Stat's
+    snapshottedSummary changes.  ``scope`` restricts the candidates to the Stats under
+    that subtree (an unknown one has none): one member map built from the tree, members
+    0 and everything else NO_GROUP.  The reference has no such query; paths are relative
+    to ``tree``'s root, as in flattenMetricsTree."""
+    from ._native import NO_GROUP
+    scope = tuple(scope)
+    paths = {}
+    for path, t in tree.walk():  # the id -> path map, from one walk
+        m = t.metric
+        if isinstance(m, Metric.Stat) and m.series_id is not None:
+            paths[m.series_id] = path
+    group = None
+    if scope or int(min_count) < 1:  # (min_count = 0 admits empty rows: then only rows that Stats own)
+        group = np.full(engine.capacity, NO_GROUP, dtype=np.uint32)
+        for sid, path in paths.items():
+            if path[:len(scope)] == scope:
+                group[sid] = 0
+    res = engine.top(k, by, order=order, min_count=min_count, group=group, g=0)
+    ids, summ = res[0], res[1]
+    out = []
+    for j, sid in enumerate(ids.tolist()):
+        path = paths.get(sid)
+        if path is None:
+            continue  # (a Stat registered after the walk)
+        item = (path, HistogramSummary.from_record(summ[j]))
+        out.append(item + (int(res[2][j]),) if len(res) > 2 else item)
+    return out
