@@ -361,6 +361,13 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 // profiles/r04r_ab.txt, r04s_ab.txt).  A run that does not fit is dropped and flagged; pass 1 (the redo) exits unless k_rfix1 asked for it and adds nothing to
 // sumfix or the error counter.
 //
+// Barriers per sub-chunk: B1 (counts complete), B1b (the scan's wave totals), B2 (offsets,
+// run ranks, heads; every slot-order record read), B3 (stage sorted, group prefixes, deltas)
+// and B4 after the write-out.  While it ranks, a wave lowers its issue priority group by group
+// (b1_progress_prio), so that the waves reach B1 together.  Measured and not kept
+// (profiles/level1_overlap_ab.txt): without B4 -- each wave staging its slot-order records in
+// the stage words it writes out itself -- level 1 is 0.06-0.08 ms slower, without B1b equal.
+//
 // Direct value sums: u32 per direct series in LDS, added to sumfix by each workgroup at
 // the end of its slab.  A u32 sum cannot wrap:
 //  - only payloads below DSUM_PMAX = 2^17 are added to it.  The ranking loop's fast test
@@ -389,18 +396,30 @@ __global__ __launch_bounds__(1024) void k_rplan1(size_t n, uint32_t F, const uin
 #ifdef L5DH_PHASES  // development (tools/mk_var.sh, tools/time_lib.py): per-workgroup phase times
 __device__ unsigned long long g_phase1[1024 * 8];
 __device__ unsigned long long g_phase3[1024 * 8];  // level 2
-#define PH_INIT unsigned long long ph_acc[7] = {0, 0, 0, 0, 0, 0, 0}, ph_t = wall_clock64();
+// Two threads stamp: thread 0 (wave 0, row blockIdx.x of g_phase1) and lane 0 of the last wave
+// (row 512 + blockIdx.x), so that the wait at B1 (phase 7; phase 3 ends before B1) is seen
+// from the workgroup's first and last wave.  Phases 0-6 fill a row's
+// words 0-6 and word 7 counts launches; phase 7 goes to row 768 + blockIdx.x (word 0 thread 0,
+// word 1 the last wave).  The extra rows are written by grids of <= 256 workgroups only.
+#define PH_INIT                                                            \
+  const bool ph_on = threadIdx.x == 0 || threadIdx.x == NT1 - 64;          \
+  uint32_t ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_t = (uint32_t)wall_clock64(); /* (32-bit: a launch is < 43 s) */
 #define PH_VWAIT asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #define PH_MARK(k)                                 \
-  if (threadIdx.x == 0) {                          \
-    const unsigned long long ph_n = wall_clock64(); \
+  if (ph_on) {                                     \
+    const uint32_t ph_n = (uint32_t)wall_clock64(); \
     ph_acc[k] += ph_n - ph_t;                      \
     ph_t = ph_n;                                   \
   }
-#define PH_FLUSH                                                                   \
-  if (threadIdx.x == 0 && pass == 0) {                                             \
-    for (int k = 0; k < 7; ++k) g_phase1[blockIdx.x * 8 + k] += ph_acc[k];          \
-    g_phase1[blockIdx.x * 8 + 7] += 1;                                             \
+#define PH_FLUSH                                                                          \
+  if (ph_on && pass == 0 && (threadIdx.x == 0 || gridDim.x <= 256)) {                      \
+    const uint32_t ph_row = blockIdx.x + (threadIdx.x ? 512u : 0u);                       \
+    for (int k = 0; k < 7; ++k) g_phase1[ph_row * 8 + k] += ph_acc[k];                    \
+    g_phase1[ph_row * 8 + 7] += 1;                                                        \
+    if (gridDim.x <= 256) {                                                               \
+      g_phase1[(768 + blockIdx.x) * 8 + (threadIdx.x ? 1 : 0)] += ph_acc[7];              \
+      if (threadIdx.x == 0) g_phase1[(768 + blockIdx.x) * 8 + 7] += 1;                    \
+    }                                                                                     \
   }
 #else
 #define PH_INIT
@@ -556,6 +575,22 @@ __device__ __forceinline__ bool b1_group_invalid(Bin1Half x, int g, uint32_t S) 
 #pragma unroll
   for (int q = 0; q < B1_GS; ++q) bad |= x.s[g + q] >= S;
   return bad;
+}
+
+// The wave's issue priority while it ranks its `gi`-th group of the sub-chunk: 3, 2, 1, 0 -- a
+// wave that is behind in the ranking goes before one that is ahead.  At equal priority a SIMD
+// issues its oldest wave first, so the workgroup's first waves ran ahead and then stood at B1
+// while the last waves ranked with nobody left to cover their LDS latency: thread 0 waited
+// there for 21 % of the kernel, the last wave for 2 % (phase stamps, C3).  With the priority
+// falling as a wave advances the waves reach B1 closer together: thread 0's wait 8 %, level 1
+// -0.07 ms on C3 (profiles/level1_overlap_ab.txt).  The last group leaves every wave at 0 for
+// the phases between the barriers.
+static_assert(B1_PT / B1_GS == 4, "one priority level per group of a sub-chunk");
+__device__ __forceinline__ void b1_progress_prio(int gi) {
+  if (gi == 0) __builtin_amdgcn_s_setprio(3);
+  else if (gi == 1) __builtin_amdgcn_s_setprio(2);
+  else if (gi == 2) __builtin_amdgcn_s_setprio(1);
+  else __builtin_amdgcn_s_setprio(0);
 }
 
 // Ranks the B1_GS slots g .. of half h: payload, record, bin, the rank atomic, the direct
@@ -863,13 +898,15 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
         // the rest of its ranking): bin1 3.25-3.30 -> 3.18 ms on C3 (issued before the first group,
         // or at the second half's start as in round 4, 3.36 / 3.25; profiles/r05w_second_half_ab.txt)
         if (h == 0 && g == B1_GS && full) sh = b1_issue_half(series, values, c0, 1);
+        b1_progress_prio(h * (B1_PH / B1_GS) + g / B1_GS);
         if (full) bad |= b1_group_invalid(hf, g, S);
         const uint4 p4 = b1_rank_group(smem, h, g, hf, series, values, c0, S, FS, TB, tb, sumfix, pass);
         pk[h * B1_PH + g] = p4.x; pk[h * B1_PH + g + 1] = p4.y; pk[h * B1_PH + g + 2] = p4.z; pk[h * B1_PH + g + 3] = p4.w;
       }
     }
-    __syncthreads();  // B1: counts complete
     PH_MARK(3)
+    __syncthreads();  // B1: counts complete
+    PH_MARK(7)
     // (this phase's per-thread addresses are computed here, once per sub-chunk, not hoisted
     // out of the sub-chunk loop into registers the ranking needs)
     uint32_t tq = threadIdx.x;

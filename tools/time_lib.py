@@ -58,6 +58,17 @@ def main():
             continue
         a = snap_phases(f)
         d = [[a[w][k] - b[w][k] for k in range(8)] for w in range(1024)]
+        if name == "level1" and any(x[7] > 0 for x in d[768:]):
+            # k_rbin1w of a grid of <= 256 workgroups: rows 0.. thread 0, rows 512.. the last
+            # wave's lane 0, rows 768.. the wait at B1 (word 0 thread 0, word 1 the last wave)
+            for who, rows, col in (("wave 0", d[:256], 0), ("wave 15", d[512:768], 1)):
+                act = [x for x in rows if x[7] > 0]
+                wait = sum(x[col] for x in d[768:]) / sum(x[7] for x in d[768:]) * 0.01
+                per = [sum(x[k] for x in act) / sum(x[7] for x in act) * 0.01 for k in range(7)] + [wait]
+                print(f"  phases level1 {who} ({len(act)} wgs, us per launch per wg): " +
+                      " ".join(f"p{k}={v:.1f}" for k, v in enumerate(per)) + f"  (p7 = wait at B1; sum {sum(per):.1f})",
+                      flush=True)
+            continue
         act = [x for x in d if x[7] > 0]
         if not act:
             continue
