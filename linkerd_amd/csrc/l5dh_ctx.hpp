@@ -1,12 +1,13 @@
-// l5dh_ctx.hpp -- private to the host side (l5dh_engine.cpp, l5dh_fleet.cpp): the
-// context behind the C-ABI's opaque l5dh_ctx, the owner of its device memory, and
-// the helpers both files share (defined in l5dh_engine.cpp).
+// l5dh_ctx.hpp -- private to the host side (l5dh_engine.cpp, l5dh_queries.cpp,
+// l5dh_fleet.cpp): the context behind the C-ABI's opaque l5dh_ctx, the owner of its
+// device memory, and the helpers the files share (defined in l5dh_engine.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -214,6 +215,8 @@ int flush_ring(l5dh_ctx* c);
 // whole series space into `out` (fused path); otherwise fold into state.  encode: the
 // fleet merge's sparse export (out.words / out.roff / out.totals; out.enc is set here).
 int aggregate(l5dh_ctx* c, int final_mode, int reset, Outputs out, bool encode = false);
+// Fold the pending segments into the state rows.
+int fold(l5dh_ctx* c);
 
 // ---- staging: a caller's array is used in place when it is device memory the kernels
 // can address, otherwise through a staging buffer of the context.  Alignment: 8 bytes
@@ -263,5 +266,26 @@ struct StagedOut {
     return 0;
   }
 };
+
+// ---- the steps the drivers of the live queries share; no timer either ----
+// The state rows made current: the ring binned, the pending segments folded.
+int live_begin(l5dh_ctx* c);
+// The per-series snapshot (summ_dev, nullable) and reset of [first, first + count), from
+// the state rows.
+int rows_of_range(l5dh_ctx* c, uint32_t first, uint32_t count, Summary88* summ_dev, int reset);
+// -EINVAL unless [first, first + count) lies within the series space.
+int check_range(l5dh_ctx* c, uint32_t first, uint32_t count);
+
+// n elements of a small host or device array to the host: one copy, and one wait if it
+// was device memory.
+template <class T>
+int fetch_small(l5dh_ctx* c, const T* p, size_t n, T* host_dst) {
+  if (!is_device_ptr(p)) {
+    memcpy(host_dst, p, n * sizeof(T));
+    return 0;
+  }
+  HIPCHK(c, hipMemcpyAsync(host_dst, p, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  return sync_stream(c);
+}
 
 }  // namespace l5dh

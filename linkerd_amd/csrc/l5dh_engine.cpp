@@ -1,6 +1,7 @@
 // l5dh_engine.cpp -- host side of the MI355X histogram engine: the context's
-// lifetime, ingest, snapshot, label rollups, and the C-ABI declared in
-// include/l5dhist.h (the fleet merge's entry points are in l5dh_fleet.cpp).
+// lifetime, ingest, snapshot, and their part of the C-ABI declared in
+// include/l5dhist.h (the query families' entry points are in l5dh_queries.cpp,
+// the fleet merge's in l5dh_fleet.cpp).
 //
 // One context = one GPU = one shard of the series space (l5dh_ctx.hpp).  It owns:
 //   * the constant tables, built once per process on the host (l5dh_tables.cpp)
@@ -26,7 +27,6 @@
 #include <vector>
 
 #include "l5dh_ctx.hpp"
-#include "l5dh_fmt.hpp"
 
 using namespace l5dh;
 
@@ -91,7 +91,7 @@ int do_ingest(l5dh_ctx* c, const uint32_t* series, const float* values, size_t n
 
 }  // namespace
 
-// ---- helpers shared with l5dh_fleet.cpp (declared in l5dh_ctx.hpp) ----
+// ---- helpers shared with l5dh_queries.cpp and l5dh_fleet.cpp (declared in l5dh_ctx.hpp) ----
 namespace l5dh {
 
 int fail(l5dh_ctx* c, int code, const std::string& msg) {
@@ -242,14 +242,31 @@ int flush_ring(l5dh_ctx* c) {
   return do_ingest(c, c->ring_series.as<const uint32_t>(), c->ring_values.as<const float>(), n);
 }
 
-}  // namespace l5dh
-
-namespace {
-
 int fold(l5dh_ctx* c) {
   Outputs none{nullptr, nullptr, 0, 0, nullptr};
   return aggregate(c, 0, 0, none);
 }
+
+int live_begin(l5dh_ctx* c) {
+  int r;
+  if ((r = flush_ring(c)) || (r = fold(c))) return r;
+  return 0;
+}
+
+int rows_of_range(l5dh_ctx* c, uint32_t first, uint32_t count, Summary88* summ_dev, int reset) {
+  HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{summ_dev, nullptr, first, count, nullptr}, reset,
+                        nullptr, c->stream));
+  return 0;
+}
+
+int check_range(l5dh_ctx* c, uint32_t first, uint32_t count) {
+  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  return 0;
+}
+
+}  // namespace l5dh
+
+namespace {
 
 // Invalid series ids: k_rbin1 (k_fold1) adds to the device counter d_err (never
 // reset); k_rfix1 (a copy, after k_fold1) puts it into the pinned, mapped h_header[PIN_ERR].  The host value only grows, so comparing it with the number of
@@ -439,7 +456,7 @@ int ingest_impl(l5dh_ctx* c, const uint32_t* series, const float* values, size_t
 bool full_range(l5dh_ctx* c, uint32_t first, uint32_t count) { return first == 0 && count == c->S; }
 
 int do_snapshot(l5dh_ctx* c, uint32_t first, uint32_t count, l5dh_summary* out, int32_t* counts_out, int reset) {
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (int r = check_range(c, first, count)) return r;
   if (count == 0) return 0;
   int r = flush_ring(c);
   if (r) return r;
@@ -467,531 +484,6 @@ int do_snapshot(l5dh_ctx* c, uint32_t first, uint32_t count, l5dh_summary* out, 
   // of l5dh_ingest), so the caller's later work on that stream sees them
   if (!summ.staged() && !cnt.staged() && c->stream != c->own_stream) return 0;
   return sync_stream(c);
-}
-
-// ---- label rollups -------------------------------------------------------------
-// Per-group sums of the live state rows of series [first, first + count) (ext ==
-// nullptr; then also the per-series snapshot / reset of the same state) or of external
-// dense rows ext[count][1798].  The caller holds the lock and has checked the arguments.
-int do_rollup(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const int64_t* ext_totals,
-              const uint32_t* group, uint32_t G, l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out,
-              l5dh_summary* series_out, int reset) {
-  int r;
-  const bool live = ext == nullptr;
-  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
-  RollupWork w{};
-  w.count = count;
-  w.G = G;
-  w.first = first;
-  w.item = c->rollup_item;
-  w.caps = rollup_caps(count, G, w.item);
-  w.tmp_bytes = rollup_tmp_bytes(G);
-  const size_t G1 = (size_t)G + 1;
-  if ((r = ensure(c, c->ru_u32, (4 * G1 + RH_WORDS) * 4)) || (r = ensure(c, c->ru_u64, 2 * G1 * 8)) ||
-      (r = ensure(c, c->ru_members, ((size_t)count + 1) * 4)) || (r = ensure(c, c->ru_igroup, w.caps.items * 4)) ||
-      (r = ensure(c, c->ru_mlist, (w.caps.multi + 1) * 4)) ||
-      (r = ensure(c, c->ru_partial, (w.caps.slots + 1) * (size_t)RU_PROW * 8)) ||
-      (r = ensure(c, c->ru_tmp, w.tmp_bytes)))
-    return r;
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    // (the u32 map is the one argument that needs 4-byte alignment only; live: ext_totals is null)
-    if ((r = stage_in(c, group, count, 4, c->ru_group)) ||
-        (r = stage_in(c, ext, (size_t)count * NB, 8, c->stage_in_counts)) ||
-        (r = stage_in(c, ext_totals, count, 8, c->stage_in_totals)))
-      return r;
-  }
-  w.group = group;
-  uint32_t* u = c->ru_u32.as<uint32_t>();
-  w.cnt = u;
-  w.nitems = u + G1;
-  w.cursor = u + 2 * G1;
-  w.pbase = u + 3 * G1;
-  w.hdr = u + 4 * G1;
-  w.moff = c->ru_u64.as<uint64_t>();
-  w.ioff = w.moff + G1;
-  w.members = c->ru_members.as<uint32_t>();
-  w.igroup = c->ru_igroup.as<uint32_t>();
-  w.mlist = c->ru_mlist.as<uint32_t>();
-  w.partial = c->ru_partial.as<uint64_t>();
-  w.tmp = c->ru_tmp.p;
-  StagedOut<Summary88> g_summ, s_summ;
-  StagedOut<int32_t> g_cnt;
-  StagedOut<int64_t> g_tot;
-  if ((r = g_summ.begin(c, g_out, G, c->ru_summ)) || (r = g_cnt.begin(c, g_counts_out, (size_t)G * NB, c->ru_counts)) ||
-      (r = g_tot.begin(c, g_totals_out, G, c->ru_totals)) || (r = s_summ.begin(c, series_out, count, c->stage_summ)))
-    return r;
-  RollupOut o{g_summ.dev, g_cnt.dev, g_tot.dev};
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, launch_rollup(w, state(c), ext, ext_totals, tables(c), o, c->stream));
-  }
-  // the device's findings (an invalid map entry, a bucket sum out of range) end the call
-  // here, before the snapshot that would reset the range
-  uint32_t hdr[RH_WORDS];
-  HIPCHK(c, hipMemcpyAsync(hdr, w.hdr, sizeof(hdr), hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c))) return r;
-  if (hdr[RH_BOUNDS]) return fail(c, -EIO, "internal: a rollup workspace bound was hit");
-  if (hdr[RH_BADIDX] != 0xFFFFFFFFu)
-    return fail(c, -EINVAL,
-                "rollup: group[" + std::to_string(hdr[RH_BADIDX]) + "] is neither < ngroups nor L5DH_NO_GROUP");
-  if (hdr[RH_RANGE] != 0xFFFFFFFFu)
-    return fail(c, -ERANGE, "rollup: a bucket sum of group " + std::to_string(hdr[RH_RANGE]) + " exceeds 2^31 - 1");
-  if (live && count && (s_summ.dev || reset)) {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{s_summ.dev, nullptr, first, count, nullptr},
-                          reset, nullptr, c->stream));
-  }
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = g_summ.end(c)) || (r = g_cnt.end(c)) || (r = g_tot.end(c)) || (r = s_summ.end(c))) return r;
-  }
-  return sync_stream(c);
-}
-
-// ---- cumulative `le` buckets -----------------------------------------------------
-// The cuts of a call, on the host and checked: K in [1, LE_MAX], each cut in [1, NL],
-// strictly ascending.  A device array is fetched first (one small copy and wait).
-int le_fetch_cuts(l5dh_ctx* c, const uint32_t* cuts, uint32_t ncuts, LeCuts& out) {
-  if (ncuts < 1 || ncuts > LE_MAX) return fail(c, -EINVAL, "le: ncuts must be in [1, 64]");
-  if (!cuts) return fail(c, -EINVAL, "le: null cuts");
-  memset(&out, 0, sizeof(out));
-  if (is_device_ptr(cuts)) {
-    HIPCHK(c, hipMemcpyAsync(out.c, cuts, (size_t)ncuts * 4, hipMemcpyDeviceToHost, c->stream));
-    if (int r = sync_stream(c)) return r;
-  } else {
-    memcpy(out.c, cuts, (size_t)ncuts * 4);
-  }
-  for (uint32_t k = 0; k < ncuts; ++k) {
-    if (out.c[k] < 1 || out.c[k] > (uint32_t)NL)
-      return fail(c, -EINVAL, "le: cuts[" + std::to_string(k) + "] is outside [1, 1797]");
-    if (k && out.c[k] <= out.c[k - 1])
-      return fail(c, -EINVAL, "le: cuts[" + std::to_string(k) + "] does not ascend strictly");
-  }
-  return 0;
-}
-
-// Cumulative counts at the cuts of the live state rows of series [first, first + count)
-// (ext == nullptr; then also the per-series snapshot / reset of the same state) or of
-// external dense rows ext[count][1798].  The caller holds the lock and has checked the
-// arguments; count > 0.
-int do_le(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const int64_t* ext_totals,
-          const LeCuts& cuts, uint32_t K, uint64_t* le_out, int64_t* sums_out, int accumulate,
-          l5dh_summary* series_out, int reset) {
-  int r;
-  const bool live = ext == nullptr;
-  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
-  StagedOut<uint64_t> le;
-  StagedOut<int64_t> sums;
-  StagedOut<Summary88> s_summ;
-  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_export_state)
-  if ((r = stage_in(c, ext, (size_t)count * NB, 8, c->stage_in_counts)) ||
-      (r = stage_in(c, ext_totals, count, 8, c->stage_in_totals)) ||
-      (r = le.begin(c, le_out, (size_t)count * (K + 1), c->le_stage)) ||
-      (r = sums.begin(c, sums_out, count, c->le_sums_stage)) ||
-      (r = s_summ.begin(c, series_out, count, c->stage_summ)))
-    return r;
-  // (an accumulating host output: its old values are staged in)
-  if (accumulate && ((r = le.load(c)) || (r = sums.load(c)))) return r;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, launch_le(state(c), first, count, ext, ext_totals, cuts, K, le.dev, sums.dev, accumulate, c->stream));
-    // the per-series snapshot and the reset of the same range, from the same state
-    if (live && (s_summ.dev || reset))
-      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{s_summ.dev, nullptr, first, count, nullptr},
-                            reset, nullptr, c->stream));
-  }
-  if ((r = le.end(c)) || (r = sums.end(c)) || (r = s_summ.end(c))) return r;
-  return sync_stream(c);
-}
-
-// ---- configurable quantiles ---------------------------------------------------------
-// The quantiles of a call, on the host and checked: K in [1, Q_MAX], each q in [0, 1]
-// (NaN fails both comparisons).  A device array is fetched first (one small copy and wait).
-int quant_fetch_q(l5dh_ctx* c, const double* q, uint32_t nq, QuantQ& out) {
-  if (nq < 1 || nq > Q_MAX) return fail(c, -EINVAL, "quantiles: nq must be in [1, 64]");
-  if (!q) return fail(c, -EINVAL, "quantiles: null q");
-  memset(&out, 0, sizeof(out));
-  if (is_device_ptr(q)) {
-    HIPCHK(c, hipMemcpyAsync(out.q, q, (size_t)nq * 8, hipMemcpyDeviceToHost, c->stream));
-    if (int r = sync_stream(c)) return r;
-  } else {
-    memcpy(out.q, q, (size_t)nq * 8);
-  }
-  for (uint32_t k = 0; k < nq; ++k)
-    if (!(out.q[k] >= 0.0 && out.q[k] <= 1.0))
-      return fail(c, -EINVAL, "quantiles: q[" + std::to_string(k) + "] is not in [0, 1]");
-  return 0;
-}
-
-// The quantiles of the live state rows of series [first, first + count) (ext == nullptr;
-// then also the per-series snapshot / reset of the same state) or of external dense rows
-// ext[count][1798].  The caller holds the lock and has checked the arguments; count > 0.
-int do_quant(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* ext, const QuantQ& qs, uint32_t K,
-             int64_t* q_out, l5dh_summary* series_out, int reset) {
-  int r;
-  const bool live = ext == nullptr;
-  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
-  StagedOut<int64_t> qo;
-  StagedOut<Summary88> s_summ;
-  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_le)
-  if ((r = stage_in(c, ext, (size_t)count * NB, 8, c->stage_in_counts)) ||
-      (r = qo.begin(c, q_out, (size_t)count * K, c->q_stage)) ||
-      (r = s_summ.begin(c, series_out, count, c->stage_summ)))
-    return r;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, launch_quant(state(c), first, count, ext, qs, K, tables(c).mid, qo.dev, c->stream));
-    // the per-series snapshot and the reset of the same range, from the same state
-    if (live && (s_summ.dev || reset))
-      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{s_summ.dev, nullptr, first, count, nullptr},
-                            reset, nullptr, c->stream));
-  }
-  if ((r = qo.end(c)) || (r = s_summ.end(c))) return r;
-  return sync_stream(c);
-}
-
-// ---- top-k selection ------------------------------------------------------------------
-// What to rank by and whom: the checked arguments the two entry points share.
-struct TopQuery {
-  int by;             // 0 .. 10: the summary field; L5DH_BY_QUANTILE: percentile(q) of the live row
-  double q;
-  int order;          // L5DH_TOP_LARGEST / L5DH_TOP_SMALLEST
-  int64_t min_count;
-  const uint32_t* group;  // nullable
-  uint32_t g, k;
-};
-
-// -EINVAL for everything a selection can be asked wrongly, before anything is enqueued.
-// by_max: the largest `by` the entry point takes.
-int top_check(l5dh_ctx* c, const TopQuery& t, int by_max, const void* ids_out, const void* n_out) {
-  if (t.k < 1 || t.k > L5DH_TOP_LIMIT) return fail(c, -EINVAL, "top: k must be in [1, 1024]");
-  if (t.by < 0 || t.by > by_max) return fail(c, -EINVAL, "top: unknown `by` for this call");
-  if (t.order != L5DH_TOP_LARGEST && t.order != L5DH_TOP_SMALLEST) return fail(c, -EINVAL, "top: order must be 0 or 1");
-  if (t.min_count < 0) return fail(c, -EINVAL, "top: min_count must be >= 0");
-  if (t.by == L5DH_BY_QUANTILE && !(t.q >= 0.0 && t.q <= 1.0)) return fail(c, -EINVAL, "top: q is not in [0, 1]");
-  if (!ids_out || !n_out) return fail(c, -EINVAL, "top: null ids_out or n_out");
-  return 0;
-}
-
-// A u32 to the caller's host or device word.
-int top_put_n(l5dh_ctx* c, uint32_t* n_out, uint32_t v) {
-  if (!is_device_ptr(n_out)) {
-    *n_out = v;
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(n_out, &v, 4, hipMemcpyHostToDevice, c->stream));
-  return sync_stream(c);
-}
-
-// The k best of `count` rows: the live state rows of series [first, first + count) (ext ==
-// nullptr; then also the K = 1 quantile pass, the per-series snapshot and the reset of the
-// same state) or external summaries ext[count] (first == 0).  The caller holds the lock and
-// has checked the arguments; 0 < count <= TOP_MAX_ROWS.
-int do_top(l5dh_ctx* c, uint32_t first, uint32_t count, const Summary88* ext, const TopQuery& t, uint32_t* ids_out,
-           l5dh_summary* top_out, int64_t* q_out, uint32_t* n_out, l5dh_summary* series_out, int reset) {
-  int r;
-  const bool live = ext == nullptr;
-  const bool byq = t.by == L5DH_BY_QUANTILE;
-  const uint32_t kp = top_kp(t.k);
-  if (live && ((r = flush_ring(c)) || (r = fold(c)))) return r;
-  StagedOut<Summary88> s_summ, top;
-  StagedOut<uint32_t> ids;
-  StagedOut<int64_t> qo;
-  const uint32_t* group = t.group;
-  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_quantiles)
-  if ((r = stage_in(c, ext, count, 8, c->top_vals)) || (r = stage_in(c, group, count, 4, c->top_group)) ||
-      (r = ensure(c, c->top_list_a, top_bytes_a(count, kp))) || (r = ensure(c, c->top_list_b, top_bytes_b(count, kp))) ||
-      (r = ensure(c, c->top_n, 4)) || (r = ids.begin(c, ids_out, t.k, c->top_ids, 4)) ||
-      (r = top.begin(c, top_out, t.k, c->top_summ)) || (r = qo.begin(c, byq ? q_out : nullptr, t.k, c->top_qout)))
-    return r;
-  // the rows ranked: the external ones, or the live range's summaries in series_out's
-  // (staged) buffer, or in the same staging buffer as scratch
-  Summary88* live_rows = nullptr;
-  if (live) {
-    if ((r = s_summ.begin(c, series_out, count, c->stage_summ))) return r;
-    live_rows = s_summ.dev;
-    if (!live_rows) {
-      if ((r = ensure(c, c->stage_summ, (size_t)count * sizeof(Summary88)))) return r;
-      live_rows = c->stage_summ.as<Summary88>();
-    }
-    if (byq && (r = ensure(c, c->top_q, (size_t)count * 8))) return r;
-  }
-  TopArgs a{};
-  a.summ = live ? live_rows : ext;
-  a.qv = byq ? c->top_q.as<const int64_t>() : nullptr;
-  a.group = group;
-  a.g = t.g;
-  a.n = count;
-  a.first = first;
-  a.by = (uint32_t)t.by;
-  a.smallest = t.order == L5DH_TOP_SMALLEST;
-  a.min_count = t.min_count;
-  a.k = t.k;
-  a.list_a = c->top_list_a.as<TopItem>();
-  a.list_b = c->top_list_b.as<TopItem>();
-  a.ids_out = ids.dev;
-  a.top_out = top.dev;
-  a.q_out = qo.dev;
-  a.n_out = c->top_n.as<uint32_t>();
-  a.n_out2 = is_device_ptr(n_out) ? n_out : nullptr;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    if (live) {
-      if (byq) {  // the existing kernel with K = 1, before any reset
-        QuantQ qs;
-        memset(&qs, 0, sizeof(qs));
-        qs.q[0] = t.q;
-        HIPCHK(c, launch_quant(state(c), first, count, nullptr, qs, 1, tables(c).mid, c->top_q.as<int64_t>(), c->stream));
-      }
-      // the per-series summaries and the reset of the same range, from the same state
-      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{live_rows, nullptr, first, count, nullptr},
-                            reset, nullptr, c->stream));
-    }
-    HIPCHK(c, launch_top(a, c->stream));
-  }
-  // the number of winners: what the host copies back of staged outputs, and no more
-  uint32_t m = 0;
-  HIPCHK(c, hipMemcpyAsync(&m, a.n_out, 4, hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c))) return r;
-  if (m > t.k) return fail(c, -EIO, "internal: top-k count out of range");
-  if (!a.n_out2) *n_out = m;
-  if (m && ids.staged()) HIPCHK(c, hipMemcpyAsync(ids.user, ids.dev, (size_t)m * 4, hipMemcpyDefault, c->stream));
-  if (m && top.staged())
-    HIPCHK(c, hipMemcpyAsync(top.user, top.dev, (size_t)m * sizeof(Summary88), hipMemcpyDefault, c->stream));
-  if (m && qo.staged()) HIPCHK(c, hipMemcpyAsync(qo.user, qo.dev, (size_t)m * 8, hipMemcpyDefault, c->stream));
-  if ((r = s_summ.end(c))) return r;
-  return sync_stream(c);
-}
-
-// ---- state import and sparse export -------------------------------------------------
-// The status words of an import, read in one copy and one wait.
-int imp_read_status(l5dh_ctx* c, uint32_t (&hs)[IS_WORDS]) {
-  HIPCHK(c, hipMemcpyAsync(hs, c->imp_status.p, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-  return sync_stream(c);
-}
-
-// Dense rows into series [first, first + count).  The caller holds the lock and has checked
-// the range; count > 0.  Nothing is flushed or folded: the ring's samples and the pending
-// segments are summed onto the rows by whichever snapshot comes next.
-int do_import_dense(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {
-  int r;
-  if ((r = ensure(c, c->imp_status, IS_WORDS * 4))) return r;
-  // (the copies are not timed here, as in l5dh_summarize_dense and l5dh_export_state)
-  if ((r = stage_in(c, counts, (size_t)count * NB, 8, c->stage_in_counts)) ||
-      (r = stage_in(c, totals, count, 8, c->stage_in_totals)))
-    return r;
-  uint32_t* status = c->imp_status.as<uint32_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, import_status_init(status, c->stream));
-    HIPCHK(c, import_dense(state(c), first, count, counts, totals, status, c->stream));
-  }
-  uint32_t hs[IS_WORDS];
-  if ((r = imp_read_status(c, hs))) return r;
-  if (hs[IS_BAD] == IS_NONE && hs[IS_RANGE] == IS_NONE) return 0;
-  {  // the same rows out again: the state reads as it did before the call
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, import_dense_undo(state(c), first, count, counts, totals, c->stream));
-  }
-  if ((r = sync_stream(c))) return r;
-  if (hs[IS_BAD] != IS_NONE)
-    return fail(c, -EINVAL, "import_state: a negative count in the row of series " + std::to_string(hs[IS_BAD]));
-  return fail(c, -ERANGE, "import_state: a bucket sum of series " + std::to_string(hs[IS_RANGE]) + " exceeds 2^31 - 1");
-}
-
-// CSR rows into the state.  The caller holds the lock; n > 0.
-int do_import_sparse(l5dh_ctx* c, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
-                     const BucketEntry* entries, const int64_t* totals) {
-  int r;
-  if (!row_off) return fail(c, -EINVAL, "import_sparse: null row_off");
-  if (n > c->S) return fail(c, -EINVAL, "import_sparse: more rows than series");
-  if (!series && (uint64_t)first + n > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  // the entry count: row_off[n] (a device array: one small copy and wait)
-  uint64_t n_entries = 0;
-  if (is_device_ptr(row_off)) {
-    HIPCHK(c, hipMemcpyAsync(&n_entries, row_off + n, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((r = sync_stream(c))) return r;
-  } else {
-    memcpy(&n_entries, row_off + n, 8);
-  }
-  if (n_entries && !entries) return fail(c, -EINVAL, "import_sparse: null entries");
-  // more entries than n full rows: some row's offsets are wrong -- the check finds the least
-  // such row from the offsets alone (no entry is staged or read)
-  const bool offsets_only = n_entries > (uint64_t)n * NB;
-  if (offsets_only) entries = nullptr;
-  if ((r = ensure(c, c->imp_status, IS_WORDS * 4)) || (r = ensure(c, c->imp_tflag, (size_t)c->F * 4)) ||
-      (r = ensure(c, c->imp_list, (size_t)c->F * 4)))
-    return r;
-  if ((r = stage_in(c, series, n, 4, c->imp_series)) || (r = stage_in(c, row_off, n + 1, 8, c->imp_off)) ||
-      (r = stage_in(c, entries, (size_t)n_entries, 8, c->imp_entries)) ||
-      (r = stage_in(c, totals, n, 8, c->stage_in_totals)))
-    return r;
-  const SparseRows rows{series, first, (uint32_t)n, row_off, entries, totals, n_entries};
-  uint32_t* status = c->imp_status.as<uint32_t>();
-  uint32_t hs[IS_WORDS];
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, import_status_init(status, c->stream));
-    HIPCHK(c, import_sparse_check(rows, c->S, status, c->stream));
-  }
-  // no state is touched before the host has read the check's findings
-  if ((r = imp_read_status(c, hs))) return r;
-  if (hs[IS_BAD] != IS_NONE)
-    return fail(c, -EINVAL,
-                "import_sparse: row " + std::to_string(hs[IS_BAD]) +
-                    " is invalid (offsets, series id, bucket order or range, or a count above 2^31 - 1)");
-  if (offsets_only) return fail(c, -EIO, "internal: import_sparse offsets");
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, import_sparse(state(c), rows, c->imp_tflag.as<uint32_t>(), c->imp_list.as<uint32_t>(), status, c->stream));
-  }
-  if ((r = imp_read_status(c, hs))) return r;
-  if (hs[IS_RANGE] == IS_NONE) return 0;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, import_sparse_undo(state(c), rows, c->stream));
-  }
-  if ((r = sync_stream(c))) return r;
-  return fail(c, -ERANGE, "import_sparse: a bucket sum of series " + std::to_string(hs[IS_RANGE]) + " exceeds 2^31 - 1");
-}
-
-// The CSR of the non-empty buckets of series [first, first + count).  The caller holds the
-// lock and has checked the arguments; count > 0.
-int do_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_off, BucketEntry* entries, size_t cap,
-                     size_t* n_entries, int64_t* totals, int reset) {
-  int r;
-  if ((r = flush_ring(c)) || (r = fold(c))) return r;
-  size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(nullptr, count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-  if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
-      (r = ensure(c, c->xs_tmp, tmp_bytes)))
-    return r;
-  uint64_t* offs = c->xs_offs.as<uint64_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, export_sparse_count(state(c), first, count, c->xs_cnt.as<uint32_t>(), c->stream));
-    HIPCHK(c, merge_count(nullptr, count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
-  }
-  // the entry count: one host wait, before anything of the caller's is written
-  uint64_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(&total, offs + count, 8, hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c))) return r;
-  *n_entries = (size_t)total;
-  if (!entries) return 0;  // a size query
-  if (cap < total)
-    return fail(c, -ERANGE, "export_sparse: " + std::to_string(total) + " entries, room for " + std::to_string(cap));
-  StagedOut<BucketEntry> ent;
-  StagedOut<int64_t> tot;
-  if ((r = ent.begin(c, entries, (size_t)total, c->xs_entries)) || (r = tot.begin(c, totals, count, c->stage_totals)))
-    return r;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, export_sparse_write(state(c), first, count, offs, ent.dev, tot.dev, c->stream));
-    // the reset of the same range, from the same state
-    if (reset)
-      HIPCHK(c, launch_rows(state(c), nullptr, nullptr, tables(c), Outputs{nullptr, nullptr, first, count, nullptr}, reset,
-                            nullptr, c->stream));
-  }
-  HIPCHK(c, hipMemcpyAsync(row_off, offs, ((size_t)count + 1) * 8, hipMemcpyDefault, c->stream));
-  if ((r = ent.end(c)) || (r = tot.end(c))) return r;  // (the copies are not timed here)
-  return sync_stream(c);
-}
-
-// ---- the device renderer -----------------------------------------------------------
-// Bytes of a name array that is not used in place: its offsets' last entry (the write
-// pass, the only reader of the bytes, runs after every offset was found ascending).
-int rd_stage_bytes(l5dh_ctx* c, const uint8_t*& bytes, const uint64_t* off, size_t n, DevBuf& stage) {
-  if (direct(bytes, 1)) return 0;
-  uint64_t last = 0;
-  if (is_device_ptr(off)) {
-    HIPCHK(c, hipMemcpyAsync(&last, off + n, 8, hipMemcpyDeviceToHost, c->stream));
-    if (int r = sync_stream(c)) return r;
-  } else {
-    last = off[n];
-  }
-  if (last && !bytes) return fail(c, -EINVAL, "render: null name bytes under non-empty offsets");
-  return stage_in(c, bytes, (size_t)last, 1, stage);
-}
-
-// The findings of the passes, in the order the header lists them.
-int rd_findings(l5dh_ctx* c, const uint32_t* f) {
-  const uint32_t none = 0xFFFFFFFFu;
-  if (f[RF_BADIDX] != none)
-    return fail(c, -EINVAL, "render: index of row " + std::to_string(f[RF_BADIDX]) + " is not < nvalues");
-  if (f[RF_BADOFF] != none)
-    return fail(c, -EINVAL, "render: key_off or lab_off descends at row " + std::to_string(f[RF_BADOFF]));
-  if (f[RF_LONG] != none)
-    return fail(c, -EINVAL, "render: key and label text of row " + std::to_string(f[RF_LONG]) + " exceed 2^25 bytes");
-  if (f[RF_RANGE] != none)
-    return fail(c, -ERANGE,
-                "render: avg of row " + std::to_string(f[RF_RANGE]) + " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
-  if (f[RF_MISMATCH] != none)
-    return fail(c, -EIO, "internal: the render passes disagree on the length of row " + std::to_string(f[RF_MISMATCH]));
-  return 0;
-}
-
-// The passes over n > 0 rows; rows holds device pointers (the caller staged the values).
-// The caller holds the lock and has checked the arguments.
-template <class Rows>
-int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, const Rows& rows, uint8_t* out, size_t cap,
-              size_t* len) {
-  int r;
-  RenderNames nm{names->index, names->key_off, names->key_bytes, names->lab_off, names->lab_bytes};
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = rd_stage_bytes(c, nm.key_bytes, names->key_off, n, c->rd_kbytes)) ||
-        (r = rd_stage_bytes(c, nm.lab_bytes, names->lab_off, n, c->rd_lbytes)) ||
-        (r = stage_in(c, nm.index, n, 4, c->rd_index)) || (r = stage_in(c, nm.key_off, n + 1, 8, c->rd_koff)) ||
-        (r = stage_in(c, nm.lab_off, n + 1, 8, c->rd_loff)))
-      return r;
-  }
-  size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(nullptr, (uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-  if ((r = ensure(c, c->rd_len, (n + 1) * 4)) || (r = ensure(c, c->rd_offs, (n + 1) * 8)) ||
-      (r = ensure(c, c->rd_flags, RF_WORDS * 4)) || (r = ensure(c, c->rd_tmp, tmp_bytes)))
-    return r;
-  uint32_t* flags = c->rd_flags.as<uint32_t>();
-  uint64_t* offs = c->rd_offs.as<uint64_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, hipMemsetAsync(flags, 0xFF, RF_WORDS * 4, c->stream));
-    HIPCHK(c, render_lengths(nm, (uint32_t)n, (uint32_t)nvalues, rows, c->rd_len.as<uint32_t>(), flags, c->stream));
-    HIPCHK(c, merge_count(nullptr, (uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
-  }
-  // the device's findings and the text's length: one host wait, before anything is written
-  uint32_t hf[RF_WORDS];
-  uint64_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c)) || (r = rd_findings(c, hf))) return r;
-  if (len) *len = (size_t)total;
-  if (!out) return 0;  // a size query
-  if (cap < total)
-    return fail(c, -ERANGE, "render: the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
-  StagedOut<uint8_t> o;
-  if ((r = o.begin(c, out, (size_t)total, c->rd_out, 1))) return r;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, render_write(nm, (uint32_t)n, rows, offs, o.dev, flags, c->stream));
-  }
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = o.end(c))) return r;
-    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  }
-  if ((r = sync_stream(c))) return r;
-  return rd_findings(c, hf);
-}
-
-// The arguments both render calls share.  0: go on; 1: n == 0, done; negative: an error.
-int rd_check(l5dh_ctx* c, const l5dh_names* names, size_t n, const void* values, size_t nvalues, size_t* len) {
-  if (len) *len = 0;
-  if (!names || !names->key_off || !names->lab_off) return fail(c, -EINVAL, "render: null names, key_off or lab_off");
-  if (n == 0) return 1;
-  if (nvalues == 0 || !values) return fail(c, -EINVAL, "render: no values for the rows");
-  if (n > 0xFFFFFFF0ull || nvalues > 0xFFFFFFFFull) return fail(c, -EINVAL, "render: more than 2^32 - 16 rows");
-  return 0;
 }
 
 }  // namespace
@@ -1136,7 +628,7 @@ int l5dh_snapshot(l5dh_ctx* c, uint32_t first, uint32_t count, l5dh_summary* out
 int l5dh_export_state(l5dh_ctx* c, uint32_t first, uint32_t count, int32_t* counts, int64_t* totals, int reset) {
   if (!c) return -EINVAL;
   CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
+  if (int r = check_range(c, first, count)) return r;
   if (count == 0) return 0;
   int r = flush_ring(c);
   if (r) return r;
@@ -1179,237 +671,12 @@ int l5dh_summarize_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* tota
   return sync_stream(c);
 }
 
-int l5dh_rollup(l5dh_ctx* c, uint32_t first, uint32_t count, const uint32_t* group, uint32_t ngroups,
-                l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out, l5dh_summary* series_out,
-                int reset) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  if (ngroups == 0 || ngroups > L5DH_MAX_SERIES) return fail(c, -EINVAL, "rollup: ngroups must be in [1, 2^20]");
-  if (!group) return fail(c, -EINVAL, "rollup: null group map");
-  return do_rollup(c, first, count, nullptr, nullptr, group, ngroups, g_out, g_counts_out, g_totals_out, series_out,
-                   reset);
-}
-
-int l5dh_rollup_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, size_t n, const uint32_t* group,
-                      uint32_t ngroups, l5dh_summary* g_out, int32_t* g_counts_out, int64_t* g_totals_out) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (n > 0xFFFFFFF0ull) return fail(c, -EINVAL, "rollup: more than 2^32 - 16 dense rows");
-  if (ngroups == 0 || ngroups > L5DH_MAX_SERIES) return fail(c, -EINVAL, "rollup: ngroups must be in [1, 2^20]");
-  if (!group) return fail(c, -EINVAL, "rollup: null group map");
-  if (n && !counts) return fail(c, -EINVAL, "rollup: null dense rows");
-  // (n == 0: the kernels never read a row; a non-null marker selects the dense source)
-  static const int32_t none = 0;
-  return do_rollup(c, 0, (uint32_t)n, n ? counts : &none, n ? totals : nullptr, group, ngroups, g_out, g_counts_out,
-                   g_totals_out, nullptr, 0);
-}
-
-int l5dh_le_cuts(const double* bounds, size_t n, uint32_t* cuts, int64_t* le) { return le_cuts(bounds, n, cuts, le); }
-
-int l5dh_le(l5dh_ctx* c, uint32_t first, uint32_t count, const uint32_t* cuts, uint32_t ncuts, uint64_t* le_out,
-            int64_t* sums_out, int accumulate, l5dh_summary* series_out, int reset) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  LeCuts lc;
-  if (int r = le_fetch_cuts(c, cuts, ncuts, lc)) return r;
-  if (count == 0) return 0;
-  if (!le_out) return fail(c, -EINVAL, "le: null output");
-  return do_le(c, first, count, nullptr, nullptr, lc, ncuts, le_out, sums_out, accumulate, series_out, reset);
-}
-
-int l5dh_le_dense(l5dh_ctx* c, const int32_t* counts, const int64_t* totals, size_t n, const uint32_t* cuts,
-                  uint32_t ncuts, uint64_t* le_out, int64_t* sums_out, int accumulate) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (n > 0xFFFFFFFFull) return fail(c, -EINVAL, "le: more than 2^32 - 1 dense rows");
-  LeCuts lc;
-  if (int r = le_fetch_cuts(c, cuts, ncuts, lc)) return r;
-  if (n == 0) return 0;
-  if (!counts || !le_out) return fail(c, -EINVAL, "le: null dense rows or output");
-  return do_le(c, 0, (uint32_t)n, counts, totals, lc, ncuts, le_out, sums_out, accumulate, nullptr, 0);
-}
-
-int l5dh_quantiles(l5dh_ctx* c, uint32_t first, uint32_t count, const double* q, uint32_t nq, int64_t* q_out,
-                   l5dh_summary* series_out, int reset) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  QuantQ qs;
-  if (int r = quant_fetch_q(c, q, nq, qs)) return r;
-  if (count == 0) return 0;
-  if (!q_out) return fail(c, -EINVAL, "quantiles: null output");
-  return do_quant(c, first, count, nullptr, qs, nq, q_out, series_out, reset);
-}
-
-int l5dh_quantiles_dense(l5dh_ctx* c, const int32_t* counts, size_t n, const double* q, uint32_t nq, int64_t* q_out) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (n > 0xFFFFFFFFull) return fail(c, -EINVAL, "quantiles: more than 2^32 - 1 dense rows");
-  QuantQ qs;
-  if (int r = quant_fetch_q(c, q, nq, qs)) return r;
-  if (n == 0) return 0;
-  if (!counts || !q_out) return fail(c, -EINVAL, "quantiles: null dense rows or output");
-  return do_quant(c, 0, (uint32_t)n, counts, qs, nq, q_out, nullptr, 0);
-}
-
-int l5dh_top(l5dh_ctx* c, uint32_t first, uint32_t count, int by, double q, int order, int64_t min_count,
-             const uint32_t* group, uint32_t g, uint32_t k, uint32_t* ids_out, l5dh_summary* top_out, int64_t* q_out,
-             uint32_t* n_out, l5dh_summary* series_out, int reset) {
-  if (!c) return -EINVAL;
-  CtxLock lk(c);
-  static_assert(L5DH_TOP_LIMIT == TOP_LIMIT && L5DH_BY_QUANTILE == TOP_BY_QUANTILE && L5DH_BY_AVG == TOP_BY_FIELDS - 1,
-                "the header's constants are the kernels'");
-  const TopQuery t{by, q, order, min_count, group, g, k};
-  if (int r = top_check(c, t, L5DH_BY_QUANTILE, ids_out, n_out)) return r;
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  if (count == 0) return top_put_n(c, n_out, 0);
-  return do_top(c, first, count, nullptr, t, ids_out, top_out, q_out, n_out, series_out, reset);
-}
-
-int l5dh_top_summaries(l5dh_ctx* c, const l5dh_summary* values, size_t n, int by, int order, int64_t min_count,
-                       const uint32_t* group, uint32_t g, uint32_t k, uint32_t* ids_out, l5dh_summary* top_out,
-                       uint32_t* n_out) {
-  if (!c) return -EINVAL;
-  CtxLock lk(c);
-  const TopQuery t{by, 0.0, order, min_count, group, g, k};
-  if (int r = top_check(c, t, L5DH_BY_AVG, ids_out, n_out)) return r;
-  if (n > TOP_MAX_ROWS) return fail(c, -EINVAL, "top: more than 2^24 rows");
-  if (n == 0) return top_put_n(c, n_out, 0);
-  if (!values) return fail(c, -EINVAL, "top: null values");
-  static_assert(sizeof(l5dh_summary) == sizeof(Summary88), "l5dh_summary layout");
-  return do_top(c, 0, (uint32_t)n, reinterpret_cast<const Summary88*>(values), t, ids_out, top_out, nullptr, n_out,
-                nullptr, 0);
-}
-
-int l5dh_import_state(l5dh_ctx* c, uint32_t first, uint32_t count, const int32_t* counts, const int64_t* totals) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  if (count == 0) return 0;
-  if (!counts) return fail(c, -EINVAL, "import_state: null counts");
-  return do_import_dense(c, first, count, counts, totals);
-}
-
-int l5dh_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_off, l5dh_bucket_entry* entries,
-                       size_t cap, size_t* n_entries, int64_t* totals, int reset) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if ((uint64_t)first + count > c->S) return fail(c, -EINVAL, "series range out of bounds");
-  if (!n_entries) return fail(c, -EINVAL, "export_sparse: null n_entries");
-  if (entries && !row_off) return fail(c, -EINVAL, "export_sparse: null row_off");
-  if (count == 0) {
-    *n_entries = 0;
-    if (entries) {  // (an empty range still has its row_off[0] = 0)
-      const uint64_t zero = 0;
-      HIPCHK(c, hipMemcpyAsync(row_off, &zero, 8, hipMemcpyDefault, c->stream));
-      return sync_stream(c);
-    }
-    return 0;
-  }
-  static_assert(sizeof(l5dh_bucket_entry) == sizeof(BucketEntry), "l5dh_bucket_entry layout");
-  return do_export_sparse(c, first, count, row_off, reinterpret_cast<BucketEntry*>(entries), cap, n_entries, totals,
-                          reset);
-}
-
-int l5dh_import_sparse(l5dh_ctx* c, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
-                       const l5dh_bucket_entry* entries, const int64_t* totals) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (n == 0) return 0;
-  return do_import_sparse(c, series, first, n, row_off, reinterpret_cast<const BucketEntry*>(entries), totals);
-}
-
-int l5dh_format_double(double x, char* out, size_t* len) {
-  if (!out || !len) return -EINVAL;
-  const int n = fmt::format_double(x, out);
-  *len = n < 0 ? 0 : (size_t)n;
-  return n < 0 ? -ERANGE : 0;
-}
-
-int l5dh_format_long(int64_t v, char* out, size_t* len) {
-  if (!out || !len) return -EINVAL;
-  *len = (size_t)fmt::format_long(v, out);
-  return 0;
-}
-
-int l5dh_format_ulong(uint64_t v, char* out, size_t* len) {
-  if (!out || !len) return -EINVAL;
-  *len = (size_t)fmt::format_ulong(v, out);
-  return 0;
-}
-
-int l5dh_render_summaries(l5dh_ctx* c, const l5dh_names* names, size_t n, const l5dh_summary* values, size_t nvalues,
-                          uint8_t* out, size_t cap, size_t* len) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  int r = rd_check(c, names, n, values, nvalues, len);
-  if (r) return r < 0 ? r : 0;
-  const Summary88* v = reinterpret_cast<const Summary88*>(values);
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = stage_in(c, v, nvalues, 8, c->rd_vals))) return r;
-  }
-  if ((r = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT))) return r;
-  return do_render(c, names, n, nvalues, SummaryRows{v, c->rd_avg.as<uint8_t>()}, out, cap, len);
-}
-
-int l5dh_render_le(l5dh_ctx* c, const l5dh_names* names, size_t n, const uint64_t* le_rows, const int64_t* sums,
-                   size_t nvalues, const int64_t* le, uint32_t ncuts, uint8_t* out, size_t cap, size_t* len) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (len) *len = 0;
-  if (ncuts < 1 || ncuts > L5DH_LE_MAX) return fail(c, -EINVAL, "render: ncuts must be in [1, 64]");
-  int r = rd_check(c, names, n, le_rows, nvalues, len);
-  if (r) return r < 0 ? r : 0;
-  if (!le) return fail(c, -EINVAL, "render: null le labels");
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = stage_in(c, le_rows, nvalues * ((size_t)ncuts + 1), 8, c->rd_vals)) ||
-        (r = stage_in(c, sums, nvalues, 8, c->rd_sums)) || (r = stage_in(c, le, (size_t)ncuts, 8, c->rd_le)))
-      return r;
-  }
-  return do_render(c, names, n, nvalues, LeRows{le_rows, sums, le, ncuts}, out, cap, len);
-}
-
-int l5dh_render_quantiles(l5dh_ctx* c, const l5dh_names* names, size_t n, const int64_t* q_rows, size_t nvalues,
-                          const double* q, uint32_t nq, uint8_t* out, size_t cap, size_t* len) {
-  if (!c) return -EINVAL;
-  CtxLock g(c);
-  if (len) *len = 0;
-  QuantQ qs;
-  int r = quant_fetch_q(c, q, nq, qs);
-  if (r) return r;
-  // the K labels, formatted once per call: Double.toString(q[k]), its length in the slot's last byte
-  uint8_t labels[Q_MAX * RENDER_QLABEL_SLOT] = {0};
-  static_assert(L5DH_DOUBLE_CHARS < RENDER_QLABEL_SLOT, "a label and its length share a slot");
-  for (uint32_t k = 0; k < nq; ++k) {
-    uint8_t* slot = labels + (size_t)k * RENDER_QLABEL_SLOT;
-    const int m = fmt::format_double(qs.q[k], reinterpret_cast<char*>(slot));
-    if (m < 0)
-      return fail(c, -ERANGE, "render: q[" + std::to_string(k) + "] is outside +-[2^-64, 2^64), 0, NaN, Infinity");
-    slot[RENDER_QLABEL_SLOT - 1] = (uint8_t)m;
-  }
-  r = rd_check(c, names, n, q_rows, nvalues, len);
-  if (r) return r < 0 ? r : 0;
-  const uint8_t* lab = labels;
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = stage_in(c, q_rows, nvalues * (size_t)nq, 8, c->rd_vals)) ||
-        (r = stage_in(c, lab, (size_t)nq * RENDER_QLABEL_SLOT, 1, c->rd_qlabels)))
-      return r;
-  }
-  // (labels lives on this frame: do_render returns only after the stream has drained)
-  return do_render(c, names, n, nvalues, QuantRows{q_rows, lab, nq}, out, cap, len);
-}
-
 int l5dh_peek(l5dh_ctx* c, uint32_t series, l5dh_bucket_count* out, size_t cap, size_t* n_out) {
   if (!c) return -EINVAL;
   CtxLock g(c);
   if (series >= c->S) return fail(c, -EINVAL, "series id out of range");
-  int r;
-  if ((r = flush_ring(c)) || (r = fold(c))) return r;
+  int r = live_begin(c);
+  if (r) return r;
   uint8_t dirty = 0;
   std::vector<uint32_t> row(ROW, 0);
   HIPCHK(c, hipMemcpyAsync(&dirty, c->d_dirty + (series >> TILE_SHIFT), 1, hipMemcpyDeviceToHost, c->stream));

@@ -33,7 +33,7 @@
 // which reads exactly as a clean tile does.
 #include <algorithm>
 
-#include "l5dh_device.hpp"
+#include "l5dh_lanerow.hpp"
 #include "l5dh_import.hpp"
 
 namespace l5dh {
@@ -41,36 +41,6 @@ namespace {
 
 constexpr uint32_t CMAX = (uint32_t)INT_MAXV;  // 2^31 - 1: the largest count of an int32 row
 
-// Lane 63's groups 7 and 8 (bins 1792..1797) loaded in one place, by every lane (the other
-// lanes at their own first bins, lines their groups 0 and 1 already bring) -- a load under
-// `if (lane == 63)` makes the wave wait for everything in flight at the join.
-__device__ __forceinline__ void tail_state(const uint32_t* __restrict__ row, bool tail, int own, uint4& t7, uint4& t8) {
-  const uint4 a = *reinterpret_cast<const uint4*>(row + (tail ? 1792 : own));
-  const uint4 b = *reinterpret_cast<const uint4*>(row + (tail ? 1796 : own));  // (rows are padded to ROW words)
-  t7 = tail ? a : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b.x, b.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-__device__ __forceinline__ void tail_ext(const int32_t* __restrict__ row, bool tail, int own, uint4& t7, uint4& t8) {
-  const int32_t* p = row + (tail ? 1792 : own);  // own <= 28 * 62: p + 5 stays inside the row
-  const uint2 a0 = *reinterpret_cast<const uint2*>(p), a1 = *reinterpret_cast<const uint2*>(p + 2);
-  const uint2 b0 = *reinterpret_cast<const uint2*>(p + 4);  // (lane 63: bins 1796, 1797, the row's last)
-  t7 = tail ? make_uint4(a0.x, a0.y, a1.x, a1.y) : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b0.x, b0.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-__device__ __forceinline__ void load_state(const uint32_t* __restrict__ row, uint4 (&v)[9]) {
-  const int lane = lane_id();
-  const SrcRow32 src{row};
-#pragma unroll
-  for (int q = 0; q < 7; ++q) v[q] = src.get4(28 * lane + 4 * q);
-  tail_state(row, lane == 63, 28 * lane, v[7], v[8]);
-}
-__device__ __forceinline__ void load_ext(const int32_t* __restrict__ row, uint4 (&v)[9]) {
-  const int lane = lane_id();
-  const SrcExt src{row};
-#pragma unroll
-  for (int q = 0; q < 7; ++q) v[q] = src.get4(28 * lane + 4 * q);
-  tail_ext(row, lane == 63, 28 * lane, v[7], v[8]);
-}
 // The lane's groups to a state row (lane 63: also groups 7 and 8, the padding bins zero).
 __device__ __forceinline__ void store_state(uint32_t* __restrict__ row, const uint4 (&v)[9]) {
   const int lane = lane_id();
@@ -120,10 +90,10 @@ __global__ __launch_bounds__(256) void k_imp_dense(State st, uint32_t first, uin
   }
   const size_t i = s - first;
   uint4 v[9], a[9];
-  load_ext(ext + i * NB, v);
+  lane_row_load(SrcExt{ext + i * NB}, v);
   const uint64_t t = ext_total ? (uint64_t)ext_total[i] : 0ull;
   if (dirty) {
-    load_state(row, a);
+    lane_row_load(SrcRow32{row}, a);
   } else {
 #pragma unroll
     for (int q = 0; q < 9; ++q) a[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -245,7 +215,7 @@ __global__ __launch_bounds__(256) void k_exp_count(State st, uint32_t first, uin
   uint32_t c = 0;
   if (st.dirty[s >> TILE_SHIFT] != 0) {  // (wave-uniform; a clean tile's rows are never read)
     uint4 v[9];
-    load_state(st.counts + (size_t)s * ROW, v);
+    lane_row_load(SrcRow32{st.counts + (size_t)s * ROW}, v);
     c = (uint32_t)wave_sum((uint64_t)nz_lane(v));
   }
   if (lane_id() == 0) rowcnt[i] = c;
@@ -270,7 +240,7 @@ __global__ __launch_bounds__(256) void k_exp_write(State st, uint32_t first, uin
     return;
   }
   uint4 v[9];
-  load_state(st.counts + (size_t)s * ROW, v);
+  lane_row_load(SrcRow32{st.counts + (size_t)s * ROW}, v);
   // (+ sumfix as in k_rows: a one-tile space's fold leaves its escaped samples' sums there)
   if (totals && lane == 0) totals[i] = (int64_t)((uint64_t)st.total[s] + (uint64_t)st.sumfix[s]);
   const uint32_t c = nz_lane(v);
@@ -286,7 +256,6 @@ __global__ __launch_bounds__(256) void k_exp_write(State st, uint32_t first, uin
   }
 }
 
-inline dim3 waves4(uint32_t n) { return dim3(n / 4 + (n % 4 != 0)); }
 inline dim3 threads256(uint32_t n) { return dim3(n / 256 + (n % 256 != 0)); }
 
 template <bool UNDO>

@@ -13,38 +13,11 @@
 //          cut (a statically unrolled loop of 9 shuffles), one get4 of the group the cut
 //          falls in when c % 4 != 0.  Lanes 0..K-1 write the K counts as consecutive u64
 //          words, then the row's count (word K) follows.
-#include "l5dh_device.hpp"
+#include "l5dh_lanerow.hpp"
 #include "l5dh_le.hpp"
 
 namespace l5dh {
 namespace {
-
-// Lane 63's groups 7 and 8 (bins 1792..1797) without a branch: every lane issues the two
-// loads -- the other lanes at their own first bins, lines their groups 0 and 1 already
-// bring -- and keeps zeros.  A load under `if (lane == 63)` makes the wave wait for
-// everything in flight at the branch's join, one memory round trip per group.
-__device__ __forceinline__ void le_tail(const SrcRow32& s, bool tail, int own, uint4& t7, uint4& t8) {
-  const uint4 a = *reinterpret_cast<const uint4*>(s.row + (tail ? 1792 : own));
-  const uint4 b = *reinterpret_cast<const uint4*>(s.row + (tail ? 1796 : own));  // (rows are padded to ROW words)
-  t7 = tail ? a : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b.x, b.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-__device__ __forceinline__ void le_tail(const SrcExt& s, bool tail, int own, uint4& t7, uint4& t8) {
-  const int32_t* p = s.row + (tail ? 1792 : own);  // own <= 28 * 62: p + 5 stays inside the row
-  const uint2 a0 = *reinterpret_cast<const uint2*>(p), a1 = *reinterpret_cast<const uint2*>(p + 2);
-  const uint2 b0 = *reinterpret_cast<const uint2*>(p + 4);  // (lane 63: bins 1796, 1797, the row's last)
-  t7 = tail ? make_uint4(a0.x, a0.y, a1.x, a1.y) : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b0.x, b0.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-
-// One row's groups: lane l's 7 (lane 63: 9) 16-B loads, all in flight together.
-template <class Src>
-__device__ __forceinline__ void le_load(const Src& src, uint4 (&v)[9]) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int q = 0; q < 7; ++q) v[q] = src.get4(28 * lane + 4 * q);
-  le_tail(src, lane == 63, 28 * lane, v[7], v[8]);
-}
 
 // The count at this lane's cut c (mine: the lane holds a cut; the other lanes only take
 // part in the shuffles) and the row's count, from the loaded groups.  Whole waves.
@@ -60,8 +33,7 @@ __device__ __forceinline__ void le_resolve(const uint4 (&v)[9], const Src& src, 
   for (int q = 0; q < 9; ++q) ls += sums_get(g, q);
   const uint64_t incl = wave_incl_scan(ls);
   const uint64_t excl = incl - ls;
-  num = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(incl >> 32), 63) << 32) |
-        (uint32_t)__builtin_amdgcn_readlane((uint32_t)incl, 63);
+  num = readlane64(incl, 63);
   const int owner = min((int)(c / 28u), 63);
   const int below = (int)c - 28 * owner;  // the owner's bins under the cut: 0..27 (lane 63: 0..33)
   const int nq = below >> 2, rem = below & 3;
@@ -98,7 +70,7 @@ __global__ __launch_bounds__(256) void k_le(Rows rows, const uint8_t* __restrict
     const auto src = rows.row(i);
     sum = rows.sum(i);  // (with the row's loads, not after the cut's)
     uint4 v[9];
-    le_load(src, v);
+    lane_row_load(src, v);
     le_resolve(v, src, c, mine, at_cut, num);
   }
   uint64_t* __restrict__ orow = le_out + (size_t)i * (K + 1);
@@ -115,7 +87,7 @@ hipError_t launch_le(State state, uint32_t first, uint32_t count, const int32_t*
                      hipStream_t st) {
   if (K == 0 || K > LE_MAX || !le_out) return hipErrorInvalidValue;
   if (count == 0) return hipSuccess;
-  const dim3 grid(count / 4 + (count % 4 != 0)), block(256);
+  const dim3 grid = waves4(count), block(256);
   if (ext)
     hipLaunchKernelGGL(k_le<ExtRows>, grid, block, 0, st, ExtRows{ext, ext_total}, (const uint8_t*)nullptr, 0u, count,
                        cuts, K, le_out, sums_out, accumulate);

@@ -14,38 +14,11 @@
 //            theirs: the owner's exclusive prefix by shuffle, its nine group sums (a
 //            statically unrolled loop of shuffles), one get4 of the group the target falls
 //            in, the bin, mid[bin].  Lanes 0..K-1 write the K values as consecutive i64 words.
-#include "l5dh_device.hpp"
+#include "l5dh_lanerow.hpp"
 #include "l5dh_quant.hpp"
 
 namespace l5dh {
 namespace {
-
-// Lane 63's groups 7 and 8 (bins 1792..1797) without a branch, as l5dh_le.hip has them:
-// every lane issues the two loads -- the other lanes at their own first bins, lines their
-// groups 0 and 1 already bring -- and keeps zeros.  (A load under `if (lane == 63)` makes
-// the wave wait for everything in flight at the branch's join.)
-__device__ __forceinline__ void quant_tail(const SrcRow32& s, bool tail, int own, uint4& t7, uint4& t8) {
-  const uint4 a = *reinterpret_cast<const uint4*>(s.row + (tail ? 1792 : own));
-  const uint4 b = *reinterpret_cast<const uint4*>(s.row + (tail ? 1796 : own));  // (rows are padded to ROW words)
-  t7 = tail ? a : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b.x, b.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-__device__ __forceinline__ void quant_tail(const SrcExt& s, bool tail, int own, uint4& t7, uint4& t8) {
-  const int32_t* p = s.row + (tail ? 1792 : own);  // own <= 28 * 62: p + 5 stays inside the row
-  const uint2 a0 = *reinterpret_cast<const uint2*>(p), a1 = *reinterpret_cast<const uint2*>(p + 2);
-  const uint2 b0 = *reinterpret_cast<const uint2*>(p + 4);  // (lane 63: bins 1796, 1797, the row's last)
-  t7 = tail ? make_uint4(a0.x, a0.y, a1.x, a1.y) : make_uint4(0u, 0u, 0u, 0u);
-  t8 = tail ? make_uint4(b0.x, b0.y, 0u, 0u) : make_uint4(0u, 0u, 0u, 0u);
-}
-
-// One row's groups: lane l's 7 (lane 63: 9) 16-B loads, all in flight together.
-template <class Src>
-__device__ __forceinline__ void quant_load(const Src& src, uint4 (&v)[9]) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int g = 0; g < 7; ++g) v[g] = src.get4(28 * lane + 4 * g);
-  quant_tail(src, lane == 63, 28 * lane, v[7], v[8]);
-}
 
 // The value of this lane's quantile p (mine: the lane holds one; the other lanes only take
 // part in the shuffles, with target 0) from the loaded groups.  Whole waves.
@@ -61,8 +34,7 @@ __device__ __forceinline__ int64_t quant_resolve(const uint4 (&v)[9], const Src&
   for (int k = 0; k < 9; ++k) ls += sums_get(g, k);
   const uint64_t incl = wave_incl_scan(ls);
   const uint64_t excl = incl - ls;
-  const uint64_t num = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((uint32_t)(incl >> 32), 63) << 32) |
-                       (uint32_t)__builtin_amdgcn_readlane((uint32_t)incl, 63);
+  const uint64_t num = readlane64(incl, 63);
   // 0 <= p <= 1 and num < 2^42: the product is below 2^52 and the target at most num
   const uint64_t t = mine ? (uint64_t)java_round_nonneg(__dmul_rn(p, (double)num)) : 0ull;
   // the owner: the number of lanes whose inclusive prefix is below t (t <= num = lane 63's: <= 63)
@@ -117,7 +89,7 @@ __global__ __launch_bounds__(256) void k_quant(Rows rows, const uint8_t* __restr
   if (dirty == nullptr || dirty[(first + i) >> TILE_SHIFT] != 0) {  // (wave-uniform)
     const auto src = rows.row(i);
     uint4 v[9];
-    quant_load(src, v);
+    lane_row_load(src, v);
     res = quant_resolve(v, src, p, mine, mid);
   }
   if (mine) q_out[(size_t)i * K + lane] = res;
@@ -129,7 +101,7 @@ hipError_t launch_quant(State state, uint32_t first, uint32_t count, const int32
                         const int32_t* mid, int64_t* q_out, hipStream_t st) {
   if (K == 0 || K > Q_MAX || !q_out || !mid) return hipErrorInvalidValue;
   if (count == 0) return hipSuccess;
-  const dim3 grid(count / 4 + (count % 4 != 0)), block(256);
+  const dim3 grid = waves4(count), block(256);
   if (ext)
     hipLaunchKernelGGL(k_quant<ExtRows>, grid, block, 0, st, ExtRows{ext, nullptr}, (const uint8_t*)nullptr, 0u, count, qs,
                        K, mid, q_out);
