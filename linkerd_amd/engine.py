@@ -12,6 +12,11 @@ checked (dtype, device, size) before it reaches the library.  Calls that take a
 device tensor first hand the library an event recorded on torch's current stream
 (l5dh_wait_event), so the engine's kernels run after the torch work that produced
 their inputs; calls with device outputs return once the outputs are written.
+
+Layout: every argument rule stands once, ahead of the methods that use it: ``_buf``
+(any buffer), ``_records`` (records of a structured dtype, or the words that stand for
+them), ``_rows`` with ``_whole_rows`` (the live range, or external rows), ``_u32`` and
+``_member_map``.  A query family is a ``*_into`` method -- rows, buffers, one C call.
 """
 from __future__ import annotations
 
@@ -36,6 +41,52 @@ def _is_torch(x) -> bool:
 
 def _numel(x) -> int:
     return int(x.size) if isinstance(x, np.ndarray) else int(x.numel())
+
+
+def _np_type(x):
+    """The numpy scalar type of an array or tensor (None: neither, or a dtype no call takes)."""
+    return x.dtype.type if isinstance(x, np.ndarray) else _NP_OF_TORCH.get(str(getattr(x, "dtype", None)))
+
+
+_RECORD_NOUN = {N.SUMMARY_DTYPE: "summary records", N.BUCKET_ENTRY_DTYPE: "bucket entries"}
+
+
+def _record_words(x, rec):
+    """(word dtypes, words per record) of a plain array ``x`` that stands for records of
+    ``rec``: int64 x 11 for a summary; for a bucket entry one 64-bit word, else two uint32."""
+    if rec is N.SUMMARY_DTYPE:
+        return (np.int64,), 11
+    return ((np.uint64, np.int64), 1) if _np_type(x) in (np.uint64, np.int64) else ((np.uint32, np.int32), 2)
+
+
+def _record_rows(x, rec):
+    """(whole records, words left over) of ``x``: a numpy array of ``rec`` itself, or plain words."""
+    if isinstance(x, np.ndarray) and x.dtype == rec:
+        return int(x.size), 0
+    return divmod(_numel(x), _record_words(x, rec)[1])
+
+
+def _whole_rows(counts, name: str = "dense counts") -> Optional[int]:
+    """The rows of external dense counts, which come as whole rows of 1798 buckets (None: none given)."""
+    if counts is None:
+        return None
+    n, part = divmod(_numel(counts), N.NBUCKETS)
+    if part:
+        raise ValueError(f"{name} must hold whole rows of 1798 buckets")
+    return n
+
+
+def _u32(a: np.ndarray, what: str, not_integer=None) -> np.ndarray:
+    """``a`` as uint32, converted after the range check.  not_integer: what a non-integer
+    dtype raises -- None (ingest) converts it silently, import_sparse raises ValueError,
+    the cuts TypeError (kept apart until one rule is chosen)."""
+    if a.dtype == np.dtype(np.uint32):
+        return a
+    if a.size and not_integer is not None and a.dtype.kind not in "iu":
+        raise not_integer(f"{what}: dtype {a.dtype} is not an integer type")
+    if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError(f"{what} must fit uint32")
+    return np.ascontiguousarray(a.astype(np.uint32))
 
 
 class HistogramEngine:
@@ -125,23 +176,51 @@ class HistogramEngine:
             raise ValueError(f"series range [{first}, {first + count}) outside [0, {self.max_series})")
         return first, count
 
+    def _rows(self, first: int, count: Optional[int], series, reset: bool, external: Optional[int]):
+        """(first, count) of a query's rows: the live range [first, first+count), or rows
+        0..external of data from outside (dense counts: _whole_rows; summaries), which
+        have no series snapshot and nothing to reset."""
+        if external is None:
+            return self._range(first, count)
+        if series is not None or reset:
+            raise ValueError("external rows have no series snapshot and nothing to reset")
+        return 0, external
+
+    def _records(self, x, rec, name: str, rows: int = 0, writable: bool = False, records_writable=None):
+        """Pointer of at least ``rows`` records: a numpy array of the structured dtype
+        ``rec``, or a numpy array / torch tensor of the words that stand for them
+        (_record_words; _record_rows counts them).  records_writable=False: a record
+        array is not asked to be writable (summary outputs never were; kept)."""
+        if x is None:
+            return None
+        if isinstance(x, np.ndarray) and x.dtype == rec:
+            w = writable if records_writable is None else records_writable
+            if x.size < rows or not x.flags["C_CONTIGUOUS"] or (w and not x.flags["WRITEABLE"]):
+                raise ValueError(f"{name}: needs {rows} contiguous{' writable' if w else ''} {_RECORD_NOUN[rec]}")
+            return x.ctypes.data
+        dtypes, per = _record_words(x, rec)
+        return self._buf(x, dtypes, name, rows * per, writable=writable)
+
+    def _summ_buf(self, x, rows: int, name: str):
+        """Pointer of a summary output of ``rows`` rows: int64 [rows*11] or the numpy summary dtype."""
+        return self._records(x, N.SUMMARY_DTYPE, name, rows, writable=True, records_writable=False)
+
     # -- hot path ---------------------------------------------------------------
     def ingest(self, series, values) -> None:
         """Batched Metric.Stat.add: values[i] into series[i] (u32 ids, f32 values)."""
-        if isinstance(series, np.ndarray) and series.dtype != np.uint32:
-            if series.size and (series.min() < 0 or series.max() >= 2 ** 32):
-                raise ValueError("series ids must fit uint32")
-            series = series.astype(np.uint32)
-        if isinstance(values, np.ndarray) and values.dtype != np.float32:
-            values = values.astype(np.float32)
-        series = np.ascontiguousarray(series) if isinstance(series, np.ndarray) else series
-        values = np.ascontiguousarray(values) if isinstance(values, np.ndarray) else values
+        if isinstance(series, np.ndarray):
+            series = np.ascontiguousarray(_u32(series, "series ids"))
+        if isinstance(values, np.ndarray):
+            values = np.ascontiguousarray(values, np.float32)
+        sp, vp, n = self._samples(series, values)
+        self._check(self._lib.l5dh_ingest(self._ctx, sp, vp, n), "l5dh_ingest")
+
+    def _samples(self, series, values):
+        """(series pointer, values pointer, n) of a batch: u32 (i32) ids, f32 values."""
         n = _numel(series)
         if n != _numel(values):
             raise ValueError("series and values differ in length")
-        sp = self._buf(series, (np.uint32, np.int32), "series")
-        vp = self._buf(values, (np.float32,), "values")
-        self._check(self._lib.l5dh_ingest(self._ctx, sp, vp, n), "l5dh_ingest")
+        return self._buf(series, (np.uint32, np.int32), "series"), self._buf(values, (np.float32,), "values"), n
 
     def ingest_async(self, series, values) -> int:
         """l5dh_ingest_async: returns a ticket; the buffers must stay unchanged until
@@ -149,11 +228,7 @@ class HistogramEngine:
         for name, x, dts in (("series", series, (np.uint32, np.int32)), ("values", values, (np.float32,))):
             if isinstance(x, np.ndarray) and (x.dtype.type not in dts or not x.flags["C_CONTIGUOUS"]):
                 raise TypeError(f"ingest_async: {name} must be C-contiguous {dts[0].__name__} (no conversion copy)")
-        n = _numel(series)
-        if n != _numel(values):
-            raise ValueError("series and values differ in length")
-        sp = self._buf(series, (np.uint32, np.int32), "series")
-        vp = self._buf(values, (np.float32,), "values")
+        sp, vp, n = self._samples(series, values)
         t = ctypes.c_uint64(0)
         self._check(self._lib.l5dh_ingest_async(self._ctx, sp, vp, n, ctypes.byref(t)), "l5dh_ingest_async")
         return t.value
@@ -168,9 +243,7 @@ class HistogramEngine:
         first, count = self._range(first, count)
         out = np.zeros(count, dtype=N.SUMMARY_DTYPE)
         counts = np.zeros((count, N.NBUCKETS), dtype=np.int32) if with_counts else None
-        self._check(self._lib.l5dh_snapshot(self._ctx, first, count, out.ctypes.data,
-                                            None if counts is None else counts.ctypes.data, int(reset)),
-                    "l5dh_snapshot")
+        self.snapshot_into(out, counts, first, count, reset)
         return (out, counts) if with_counts else out
 
     def snapshot_into(self, summaries=None, counts=None, first: int = 0, count: Optional[int] = None,
@@ -181,13 +254,6 @@ class HistogramEngine:
         sp = self._summ_buf(summaries, count, "summaries")
         cp = self._buf(counts, (np.int32,), "counts", count * N.NBUCKETS, writable=True)
         self._check(self._lib.l5dh_snapshot(self._ctx, first, count, sp, cp, int(reset)), "l5dh_snapshot")
-
-    def _summ_buf(self, x, rows: int, name: str):
-        if isinstance(x, np.ndarray) and x.dtype == N.SUMMARY_DTYPE:
-            if x.size < rows or not x.flags["C_CONTIGUOUS"]:
-                raise ValueError(f"{name}: needs {rows} contiguous summary records")
-            return x.ctypes.data
-        return self._buf(x, (np.int64,), name, rows * 11, writable=True)
 
     def peek(self, series: int) -> np.ndarray:
         """Metric.Stat.peek: non-empty buckets as (lower, upper, count)."""
@@ -219,29 +285,18 @@ class HistogramEngine:
         GPU) are added to series [first, first+count): each then reports what it would had
         it also received the samples behind its row.  A bucket sum above 2^31 - 1 raises
         (ERANGE), a negative count raises (EINVAL); a failing import changes nothing."""
-        count = _numel(counts) // N.NBUCKETS
-        if count * N.NBUCKETS != _numel(counts):
-            raise ValueError("counts must hold whole rows of 1798 buckets")
-        first = int(first)
-        if first < 0 or first >= 2 ** 32:
-            raise ValueError(f"first={first} does not fit uint32")
+        count = _whole_rows(counts, "counts")
+        first = self._first_u32(first)
         cp = self._buf(counts, (np.int32,), "counts")
         tp = self._buf(totals, (np.int64,), "totals", count)
         self._check(self._lib.l5dh_import_state(self._ctx, first, count, cp, tp), "l5dh_import_state")
 
-    def _entry_buf(self, x, n: int, name: str, writable: bool = False):
-        """Pointer of ``n`` l5dh_bucket_entry: a numpy array of N.BUCKET_ENTRY_DTYPE, or a
-        numpy array / torch tensor of 2n uint32 (int32) or n uint64 (int64) words."""
-        if x is None:
-            return None
-        if isinstance(x, np.ndarray) and x.dtype == N.BUCKET_ENTRY_DTYPE:
-            if x.size < n or not x.flags["C_CONTIGUOUS"] or (writable and not x.flags["WRITEABLE"]):
-                raise ValueError(f"{name}: needs {n} contiguous{' writable' if writable else ''} bucket entries")
-            return x.ctypes.data
-        dt = x.dtype.type if isinstance(x, np.ndarray) else _NP_OF_TORCH.get(str(getattr(x, "dtype", None)))
-        if dt in (np.uint64, np.int64):
-            return self._buf(x, (np.uint64, np.int64), name, n, writable=writable)
-        return self._buf(x, (np.uint32, np.int32), name, 2 * n, writable=writable)
+    @staticmethod
+    def _first_u32(first) -> int:
+        first = int(first)
+        if first < 0 or first >= 2 ** 32:
+            raise ValueError(f"first={first} does not fit uint32")
+        return first
 
     def export_sparse_size(self, first: int = 0, count: Optional[int] = None) -> int:
         """The entries ``export_sparse`` of the range would write (the size query)."""
@@ -257,22 +312,22 @@ class HistogramEngine:
         GPU): row_off uint64 (int64) [count+1], entries (N.BUCKET_ENTRY_DTYPE, or uint32
         [cap][2], or 64-bit words [cap]), totals int64 [count] or None.  Returns the entry
         count; entries too small for it raise ERANGE with nothing written or reset."""
+        rc, n = self._export_sparse(row_off, entries, totals, first, count, reset)
+        self._check(rc, "l5dh_export_sparse")
+        return n
+
+    def _export_sparse(self, row_off, entries, totals, first, count, reset):
+        """(return code, entry count) of l5dh_export_sparse into checked caller buffers."""
         first, count = self._range(first, count)
         rp = self._buf(row_off, (np.uint64, np.int64), "row_off", count + 1, writable=True)
         if row_off is None or entries is None:
             raise ValueError("row_off and entries: output buffers are needed (export_sparse_size is the size query)")
-        if isinstance(entries, np.ndarray) and entries.dtype == N.BUCKET_ENTRY_DTYPE:
-            cap = int(entries.size)
-        else:
-            words64 = (entries.dtype.type if isinstance(entries, np.ndarray)
-                       else _NP_OF_TORCH.get(str(entries.dtype))) in (np.uint64, np.int64)
-            cap = _numel(entries) if words64 else _numel(entries) // 2
-        ep = self._entry_buf(entries, 0, "entries", writable=True)
+        cap = _record_rows(entries, N.BUCKET_ENTRY_DTYPE)[0]
+        ep = self._records(entries, N.BUCKET_ENTRY_DTYPE, "entries", writable=True)
         tp = self._buf(totals, (np.int64,), "totals", count, writable=True)
         n = ctypes.c_size_t(0)
-        self._check(self._lib.l5dh_export_sparse(self._ctx, first, count, rp, ep, cap, ctypes.byref(n), tp,
-                                                 int(reset)), "l5dh_export_sparse")
-        return n.value
+        rc = self._lib.l5dh_export_sparse(self._ctx, first, count, rp, ep, cap, ctypes.byref(n), tp, int(reset))
+        return rc, n.value
 
     def export_sparse(self, first: int = 0, count: Optional[int] = None, reset: bool = False):
         """(row_off uint64 [count+1], entries N.BUCKET_ENTRY_DTYPE [row_off[count]], totals
@@ -285,13 +340,11 @@ class HistogramEngine:
         # between make the buffer too small, and the export is tried again)
         while True:
             entries = np.zeros(max(1, self.export_sparse_size(first, count)), N.BUCKET_ENTRY_DTYPE)
-            n = ctypes.c_size_t(0)
-            rc = self._lib.l5dh_export_sparse(self._ctx, first, count, row_off.ctypes.data, entries.ctypes.data,
-                                              entries.size, ctypes.byref(n), totals.ctypes.data, int(reset))
-            if rc == -errno.ERANGE and n.value > entries.size:
+            rc, n = self._export_sparse(row_off, entries, totals, first, count, reset)
+            if rc == -errno.ERANGE and n > entries.size:
                 continue
             self._check(rc, "l5dh_export_sparse")
-            return row_off, entries[:n.value], totals
+            return row_off, entries[:n], totals
 
     def import_sparse(self, row_off, entries, totals=None, first: int = 0, series=None) -> None:
         """l5dh_import_sparse: CSR rows (what ``export_sparse`` returns) are added to series
@@ -301,30 +354,25 @@ class HistogramEngine:
         n = _numel(row_off) - 1
         if n < 0:
             raise ValueError("row_off: at least one offset (row_off[0] = 0) is needed")
-        first = int(first)
-        if first < 0 or first >= 2 ** 32:
-            raise ValueError(f"first={first} does not fit uint32")
-        if isinstance(series, np.ndarray) and series.dtype != np.dtype(np.uint32):
-            if series.size and (series.dtype.kind not in "iu" or series.min() < 0 or series.max() >= 2 ** 32):
-                raise ValueError("series ids must fit uint32")
-            series = np.ascontiguousarray(series.astype(np.uint32))
+        first = self._first_u32(first)
+        if isinstance(series, np.ndarray):
+            series = _u32(series, "series ids", not_integer=ValueError)
         sp = self._buf(series, (np.uint32, np.int32), "series", n)
         if series is not None and _numel(series) != n:
             raise ValueError(f"series: {_numel(series)} ids for {n} rows")
         rp = self._buf(row_off, (np.uint64, np.int64), "row_off")
         if isinstance(row_off, np.ndarray) and isinstance(entries, np.ndarray):
-            # (the library reads row_off[n] entries: a host array is checked to hold them)
-            have = entries.size if entries.dtype == N.BUCKET_ENTRY_DTYPE else entries.nbytes // 8
+            # (the library reads row_off[n] entries: a host array is checked to hold them, counted in
+            # bytes so that an array of a dtype no entry has is still _buf's to refuse, as a TypeError)
+            have = entries.nbytes // N.BUCKET_ENTRY_DTYPE.itemsize
             if int(np.asarray(row_off).reshape(-1)[n].astype(np.uint64)) > have:
                 raise ValueError(f"entries: row_off[{n}] = {int(row_off.reshape(-1)[n])} entries, {have} given")
-        ep = self._entry_buf(entries, 0, "entries") if entries is not None and _numel(entries) else None
+        ep = self._records(entries, N.BUCKET_ENTRY_DTYPE, "entries") if entries is not None and _numel(entries) else None
         tp = self._buf(totals, (np.int64,), "totals", n)
         self._check(self._lib.l5dh_import_sparse(self._ctx, sp, first, n, rp, ep, tp), "l5dh_import_sparse")
 
     def summarize_dense(self, counts, totals, out=None):
-        n = _numel(counts) // N.NBUCKETS
-        if n * N.NBUCKETS != _numel(counts):
-            raise ValueError("counts must hold whole rows of 1798 buckets")
+        n = _whole_rows(counts, "counts")
         cp = self._buf(counts, (np.int32,), "counts")
         tp = self._buf(totals, (np.int64,), "totals", n)
         own = out is None
@@ -335,13 +383,19 @@ class HistogramEngine:
         return out if own else None
 
     # -- label rollups ------------------------------------------------------------
-    def _group_map(self, group, ngroups: int, count: int):
-        """The uint32 group map of ``count`` series (every entry < ngroups or NO_GROUP;
-        entries >= ngroups are found on the device).  A numpy int32 / int64 map is
-        converted, -1 standing for NO_GROUP."""
+    @staticmethod
+    def _ngroups(ngroups) -> int:
         ngroups = int(ngroups)
         if ngroups < 1 or ngroups > N.MAX_SERIES:
             raise ValueError(f"ngroups must be in [1, {N.MAX_SERIES}], got {ngroups}")
+        return ngroups
+
+    @staticmethod
+    def _member_map(group, rows: int, unit: str, torch_uint32_only: bool):
+        """The uint32 map of ``rows`` rows to groups.  A numpy int32 / int64 map is
+        converted, -1 standing for NO_GROUP; a torch tensor is taken as it is.
+        torch_uint32_only: the rollup refuses any other tensor dtype here, the ranking
+        leaves int32 (the same words) to _buf (kept apart until one rule is chosen)."""
         if isinstance(group, np.ndarray):
             if group.dtype in (np.dtype(np.int32), np.dtype(np.int64)):
                 if group.size and (group.min() < -1 or group.max() > N.NO_GROUP):
@@ -350,14 +404,23 @@ class HistogramEngine:
             elif group.dtype != np.dtype(np.uint32):
                 raise ValueError(f"group: dtype {group.dtype} is not uint32 (or int32 / int64 with -1 for no group)")
             group = np.ascontiguousarray(group)
-        elif _is_torch(group):
-            if _NP_OF_TORCH.get(str(group.dtype)) is not np.uint32:
-                raise ValueError(f"group: dtype {group.dtype} is not uint32")
-        else:
+        elif not _is_torch(group):
             raise ValueError(f"group: unsupported map type {type(group)!r}")
-        if _numel(group) != count:
-            raise ValueError(f"group: {_numel(group)} entries for {count} series")
-        return group, ngroups
+        elif torch_uint32_only and _np_type(group) is not np.uint32:
+            raise ValueError(f"group: dtype {group.dtype} is not uint32")
+        if _numel(group) != rows:
+            raise ValueError(f"group: {_numel(group)} entries for {rows} {unit}")
+        return group
+
+    def _group_map(self, group, ngroups: int, count: int):
+        """(map, ngroups) of a rollup of ``count`` series: every entry < ngroups or
+        NO_GROUP (entries >= ngroups are found on the device)."""
+        ngroups = self._ngroups(ngroups)
+        return self._member_map(group, count, "series", torch_uint32_only=True), ngroups
+
+    def _dense_rows(self, dcounts, dtotals, count: int):
+        """Pointers of external dense rows (counts int32 [count][1798], totals int64 [count] or None)."""
+        return self._buf(dcounts, (np.int32,), "dense counts"), self._buf(dtotals, (np.int64,), "dense totals", count)
 
     def rollup_into(self, group, ngroups: int, summaries=None, counts=None, totals=None, series=None,
                     first: int = 0, count: Optional[int] = None, reset: bool = False, dense=None) -> None:
@@ -367,24 +430,15 @@ class HistogramEngine:
         series [first, first+count) (l5dh_rollup; ``series`` then receives the per-series
         summaries of the same state and ``reset`` clears the range, atomically with the
         rollup); dense=(counts, totals) sums external dense rows (l5dh_rollup_dense)."""
-        if dense is not None:
-            dcounts, dtotals = dense
-            n = _numel(dcounts) // N.NBUCKETS
-            if n * N.NBUCKETS != _numel(dcounts):
-                raise ValueError("dense counts must hold whole rows of 1798 buckets")
-            if series is not None or reset:
-                raise ValueError("a dense rollup has no series snapshot and nothing to reset")
-            first, count = 0, n
-        else:
-            first, count = self._range(first, count)
+        dcounts, dtotals = (None, None) if dense is None else dense
+        first, count = self._rows(first, count, series, reset, _whole_rows(dcounts))
         group, ngroups = self._group_map(group, ngroups, count)
         gp = self._buf(group, (np.uint32,), "group", count)
         sp = self._summ_buf(summaries, ngroups, "summaries")
         cp = self._buf(counts, (np.int32,), "counts", ngroups * N.NBUCKETS, writable=True)
         tp = self._buf(totals, (np.int64,), "totals", ngroups, writable=True)
         if dense is not None:
-            dcp = self._buf(dcounts, (np.int32,), "dense counts")
-            dtp = self._buf(dtotals, (np.int64,), "dense totals", count)
+            dcp, dtp = self._dense_rows(dcounts, dtotals, count)
             self._check(self._lib.l5dh_rollup_dense(self._ctx, dcp, dtp, count, gp, ngroups, sp, cp, tp),
                         "l5dh_rollup_dense")
             return
@@ -394,9 +448,7 @@ class HistogramEngine:
 
     def _rollup_numpy(self, group, ngroups, with_counts, with_series, **kw):
         first, count = (0, 0) if "dense" in kw else self._range(kw.get("first", 0), kw.get("count"))
-        ngroups = int(ngroups)
-        if ngroups < 1 or ngroups > N.MAX_SERIES:
-            raise ValueError(f"ngroups must be in [1, {N.MAX_SERIES}], got {ngroups}")
+        ngroups = self._ngroups(ngroups)
         out = np.zeros(ngroups, dtype=N.SUMMARY_DTYPE)
         counts = np.zeros((ngroups, N.NBUCKETS), dtype=np.int32) if with_counts else None
         totals = np.zeros(ngroups, dtype=np.int64) if with_counts else None
@@ -441,14 +493,7 @@ class HistogramEngine:
         array (range and order are checked by the library)."""
         if _is_torch(cuts):
             return cuts
-        a = np.asarray(cuts).reshape(-1)
-        if a.dtype != np.dtype(np.uint32):
-            if a.size and a.dtype.kind not in "iu":
-                raise TypeError(f"cuts: dtype {a.dtype} is not an integer type")
-            if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
-                raise ValueError("cuts must fit uint32")
-            a = a.astype(np.uint32)
-        return np.ascontiguousarray(a)
+        return np.ascontiguousarray(_u32(np.asarray(cuts).reshape(-1), "cuts", not_integer=TypeError))
 
     def le_counts_into(self, cuts, le_out, sums=None, series=None, first: int = 0, count: Optional[int] = None,
                        reset: bool = False, accumulate: bool = False, dense=None) -> None:
@@ -460,16 +505,8 @@ class HistogramEngine:
         same state and ``reset`` clears the range, atomically with the buckets);
         dense=(counts, totals) reads external dense rows (l5dh_le_dense).  ``accumulate``
         adds to what the outputs hold: lifetime counters across resetting intervals."""
-        if dense is not None:
-            dcounts, dtotals = dense
-            n = _numel(dcounts) // N.NBUCKETS
-            if n * N.NBUCKETS != _numel(dcounts):
-                raise ValueError("dense counts must hold whole rows of 1798 buckets")
-            if series is not None or reset:
-                raise ValueError("dense rows have no series snapshot and nothing to reset")
-            first, count = 0, n
-        else:
-            first, count = self._range(first, count)
+        dcounts, dtotals = (None, None) if dense is None else dense
+        first, count = self._rows(first, count, series, reset, _whole_rows(dcounts))
         cuts = self._cuts(cuts)
         K = _numel(cuts)
         kp = self._buf(cuts, (np.uint32, np.int32), "cuts")
@@ -478,8 +515,7 @@ class HistogramEngine:
             raise ValueError("le_out: an output buffer is needed")
         tp = self._buf(sums, (np.int64,), "sums", count, writable=True)
         if dense is not None:
-            dcp = self._buf(dcounts, (np.int32,), "dense counts")
-            dtp = self._buf(dtotals, (np.int64,), "dense totals", count)
+            dcp, dtp = self._dense_rows(dcounts, dtotals, count)
             self._check(self._lib.l5dh_le_dense(self._ctx, dcp, dtp, count, kp, K, lp, tp, int(bool(accumulate))),
                         "l5dh_le_dense")
             return
@@ -508,8 +544,8 @@ class HistogramEngine:
         """The same over external dense rows (counts [n][1798] int32, totals [n] int64 or
         None), e.g. the g_counts of a rollup: cumulative buckets are linear, so these are
         the members' summed buckets."""
-        n = _numel(counts) // N.NBUCKETS
         K = _numel(self._cuts(cuts))
+        n = _whole_rows(counts)
         le, sums = np.zeros((n, K + 1), np.uint64), np.zeros(n, np.int64)
         self.le_counts_into(cuts, le, sums, dense=(counts, totals))
         return le, sums
@@ -532,15 +568,7 @@ class HistogramEngine:
         first+count) (l5dh_quantiles; ``series`` then receives the per-series summaries
         of the same state and ``reset`` clears the range, atomically with the
         quantiles); dense=counts reads external dense rows (l5dh_quantiles_dense)."""
-        if dense is not None:
-            n = _numel(dense) // N.NBUCKETS
-            if n * N.NBUCKETS != _numel(dense):
-                raise ValueError("dense counts must hold whole rows of 1798 buckets")
-            if series is not None or reset:
-                raise ValueError("dense rows have no series snapshot and nothing to reset")
-            first, count = 0, n
-        else:
-            first, count = self._range(first, count)
+        first, count = self._rows(first, count, series, reset, _whole_rows(dense))
         q = self._q(q)
         K = _numel(q)
         qp = self._buf(q, (np.float64,), "q")
@@ -568,7 +596,8 @@ class HistogramEngine:
     def quantiles_dense(self, counts, q):
         """The same over external dense rows (counts [n][1798] int32), e.g. the g_counts of
         a rollup: the exact quantiles of the members' union."""
-        out = np.zeros((_numel(counts) // N.NBUCKETS, _numel(self._q(q))), np.int64)
+        K = _numel(self._q(q))
+        out = np.zeros((_whole_rows(counts), K), np.int64)
         self.quantiles_into(q, out, dense=counts)
         return out
 
@@ -594,25 +623,6 @@ class HistogramEngine:
         except (KeyError, TypeError):
             raise ValueError(f"order: {order!r} is not 'largest' or 'smallest'") from None
 
-    def _top_group(self, group, rows: int):
-        """The uint32 member map of a ranking (None: every row): any value but ``g`` means
-        "not a member".  A numpy int32 / int64 map is converted, -1 standing for NO_GROUP."""
-        if group is None:
-            return None
-        if isinstance(group, np.ndarray):
-            if group.dtype in (np.dtype(np.int32), np.dtype(np.int64)):
-                if group.size and (group.min() < -1 or group.max() > N.NO_GROUP):
-                    raise ValueError("group: entries must be -1 (no group) or fit uint32")
-                group = np.where(group == -1, N.NO_GROUP, group).astype(np.uint32)
-            elif group.dtype != np.dtype(np.uint32):
-                raise ValueError(f"group: dtype {group.dtype} is not uint32 (or int32 / int64 with -1 for no group)")
-            group = np.ascontiguousarray(group)
-        elif not _is_torch(group):
-            raise ValueError(f"group: unsupported map type {type(group)!r}")
-        if _numel(group) != rows:
-            raise ValueError(f"group: {_numel(group)} entries for {rows} rows")
-        return group
-
     def top_into(self, k: int, by, ids, n_out, summaries=None, q_values=None, order: str = "largest",
                  min_count: int = 1, group=None, g: int = 0, first: int = 0, count: Optional[int] = None,
                  reset: bool = False, series=None, values=None) -> None:
@@ -630,19 +640,12 @@ class HistogramEngine:
             raise ValueError(f"k must be in [1, {N.TOP_LIMIT}], got {k}")
         by_i, q = self._top_by(by, allow_quantile=values is None)
         order_i = self._top_order(order)
-        if values is not None:
-            if series is not None or reset:
-                raise ValueError("external summaries have no series snapshot and nothing to reset")
-            if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
-                rows = int(values.size)
-            else:
-                rows = _numel(values) // 11
-                if rows * 11 != _numel(values):
-                    raise ValueError("values must hold whole summaries of 11 words")
-            first, count = 0, rows
-        else:
-            first, count = self._range(first, count)
-        group = self._top_group(group, count)
+        rows, part = (None, 0) if values is None else _record_rows(values, N.SUMMARY_DTYPE)
+        first, count = self._rows(first, count, series, reset, rows)
+        if part:
+            raise ValueError("values must hold whole summaries of 11 words")
+        if group is not None:
+            group = self._member_map(group, count, "rows", torch_uint32_only=False)
         gp = self._buf(group, (np.uint32, np.int32), "group", count)  # (a torch int32 map: the same words)
         ip = self._buf(ids, (np.uint32, np.int32), "ids", k, writable=True)
         np_ = self._buf(n_out, (np.uint32, np.int32), "n_out", 1, writable=True)
@@ -650,12 +653,7 @@ class HistogramEngine:
             raise ValueError("ids and n_out: output buffers are needed")
         sp = self._summ_buf(summaries, k, "summaries")
         if values is not None:
-            if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
-                if not values.flags["C_CONTIGUOUS"]:
-                    raise ValueError("values: array must be C-contiguous")
-                vp = values.ctypes.data if count else None
-            else:
-                vp = self._buf(values, (np.int64,), "values", count * 11) if count else None
+            vp = self._records(values, N.SUMMARY_DTYPE, "values", count) if count else None
             self._check(self._lib.l5dh_top_summaries(self._ctx, vp, count, by_i, order_i, int(min_count), gp, int(g), k,
                                                      ip, sp, np_), "l5dh_top_summaries")
             return
@@ -663,6 +661,13 @@ class HistogramEngine:
         rp = self._summ_buf(series, count, "series")
         self._check(self._lib.l5dh_top(self._ctx, first, count, by_i, q, order_i, int(min_count), gp, int(g), k, ip, sp, qp,
                                        np_, rp, int(reset)), "l5dh_top")
+
+    @staticmethod
+    def _top_outputs(k, by_q: bool):
+        """Host outputs (ids, n_out, summaries, q values or None) of a ranking of ``k``."""
+        kk = max(1, min(int(k), N.TOP_LIMIT))  # (an illegal k is reported by top_into)
+        return (np.zeros(kk, np.uint32), np.zeros(1, np.uint32), np.zeros(kk, dtype=N.SUMMARY_DTYPE),
+                np.zeros(kk, np.int64) if by_q else None)
 
     def top(self, k: int, by="p99", order: str = "largest", min_count: int = 1, group=None, g: int = 0,
             first: int = 0, count: Optional[int] = None, reset: bool = False, with_series: bool = False):
@@ -673,12 +678,8 @@ class HistogramEngine:
         per-series summaries of the same state follow with ``with_series``; ``reset`` clears
         the range atomically with the ranking."""
         first, count = self._range(first, count)
-        k = int(k)
         by_q = self._top_by(by)[0] == N.BY_QUANTILE
-        kk = max(1, min(k, N.TOP_LIMIT))  # (an illegal k is reported by top_into)
-        ids, n_out = np.zeros(kk, np.uint32), np.zeros(1, np.uint32)
-        summ = np.zeros(kk, dtype=N.SUMMARY_DTYPE)
-        qv = np.zeros(kk, np.int64) if by_q else None
+        ids, n_out, summ, qv = self._top_outputs(k, by_q)
         series = np.zeros(count, dtype=N.SUMMARY_DTYPE) if with_series else None
         self.top_into(k, by, ids, n_out, summ, qv, order=order, min_count=min_count, group=group, g=g, first=first,
                       count=count, reset=reset, series=series)
@@ -690,9 +691,7 @@ class HistogramEngine:
         """(row indices uint32 [n], summaries [n]) of the ``k`` best rows of external
         summaries (numpy summary dtype or int64 [n*11]; a torch tensor on the engine's GPU is
         read in place), e.g. the group summaries of a rollup: "the worst routers"."""
-        kk = max(1, min(int(k), N.TOP_LIMIT))
-        ids, n_out = np.zeros(kk, np.uint32), np.zeros(1, np.uint32)
-        summ = np.zeros(kk, dtype=N.SUMMARY_DTYPE)
+        ids, n_out, summ, _ = self._top_outputs(k, False)
         self.top_into(k, by, ids, n_out, summ, order=order, min_count=min_count, group=group, g=g, values=values)
         n = int(n_out[0])
         return ids[:n], summ[:n]
@@ -741,12 +740,7 @@ class HistogramEngine:
         Returns bytes, or with ``out`` (a uint8 numpy array or torch tensor on the
         engine's GPU) writes there and returns the length; out=QUERY writes nothing and
         returns the length the text would have."""
-        if isinstance(values, np.ndarray) and values.dtype == N.SUMMARY_DTYPE:
-            if not values.flags["C_CONTIGUOUS"]:
-                raise ValueError("values: needs contiguous summary records")
-            vp, nvalues = values.ctypes.data, int(values.size)
-        else:
-            vp, nvalues = self._buf(values, (np.int64,), "values"), _numel(values) // 11
+        vp, nvalues = self._records(values, N.SUMMARY_DTYPE, "values"), _record_rows(values, N.SUMMARY_DTYPE)[0]
         nm, n = self._names(names), names.n
         return self._render(lambda op, cap, ln: self._lib.l5dh_render_summaries(
             self._ctx, ctypes.byref(nm), n, vp, nvalues, op, cap, ln), "l5dh_render_summaries", out)
@@ -805,24 +799,26 @@ class HistogramEngine:
         self.nranks, self.rank = int(nranks), int(rank)
 
     @staticmethod
-    def comm_init_all(engines: Sequence["HistogramEngine"]) -> None:
-        arr = (ctypes.c_void_p * len(engines))(*[e._ctx.value for e in engines])
-        rc = N.load().l5dh_comm_init_all(arr, len(engines))
+    def _ctx_array(engines: Sequence["HistogramEngine"]):
+        return (ctypes.c_void_p * len(engines))(*[e._ctx.value for e in engines])
+
+    @staticmethod
+    def _comm_init_group(engines: Sequence["HistogramEngine"], entry: str) -> None:
+        rc = getattr(N.load(), entry)(HistogramEngine._ctx_array(engines), len(engines))
         if rc != 0:
-            engines[0]._check(rc, "l5dh_comm_init_all")
+            engines[0]._check(rc, entry)
         for i, e in enumerate(engines):
             e.nranks, e.rank = len(engines), i
+
+    @staticmethod
+    def comm_init_all(engines: Sequence["HistogramEngine"]) -> None:
+        HistogramEngine._comm_init_group(engines, "l5dh_comm_init_all")
 
     @staticmethod
     def comm_init_loopback(engines: Sequence["HistogramEngine"]) -> None:
         """l5dh_comm_init_loopback: the engines (one device) as an n-rank group whose
         collectives are device copies -- the multi-rank merge path on one GPU (tests)."""
-        arr = (ctypes.c_void_p * len(engines))(*[e._ctx.value for e in engines])
-        rc = N.load().l5dh_comm_init_loopback(arr, len(engines))
-        if rc != 0:
-            engines[0]._check(rc, "l5dh_comm_init_loopback")
-        for i, e in enumerate(engines):
-            e.nranks, e.rank = len(engines), i
+        HistogramEngine._comm_init_group(engines, "l5dh_comm_init_loopback")
 
     @staticmethod
     def merge_all(engines: Sequence["HistogramEngine"], mode: int = N.MERGE_REDUCE_SCATTER, with_counts: bool = False):
@@ -833,13 +829,10 @@ class HistogramEngine:
         outs = [np.zeros(rows, dtype=N.SUMMARY_DTYPE) for _ in engines]
         cnts = [np.zeros((rows, N.NBUCKETS), np.int32) for _ in engines] if with_counts else None
         tots = [np.zeros(rows, np.int64) for _ in engines] if with_counts else None
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p).value  # noqa: E731
-        ctxs = (ctypes.c_void_p * n)(*[e._ctx.value for e in engines])
-        o_arr = (ctypes.c_void_p * n)(*[ptr(o) for o in outs])
-        c_arr = (ctypes.c_void_p * n)(*[ptr(c) for c in cnts]) if with_counts else None
-        t_arr = (ctypes.c_void_p * n)(*[ptr(t) for t in tots]) if with_counts else None
+        ptrs = lambda arrs: arrs and (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
         firsts, counts = (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
-        rc = N.load().l5dh_merge_all(ctxs, n, int(mode), o_arr, c_arr, t_arr, firsts, counts)
+        rc = N.load().l5dh_merge_all(HistogramEngine._ctx_array(engines), n, int(mode), ptrs(outs), ptrs(cnts),
+                                     ptrs(tots), firsts, counts)
         if rc != 0:
             engines[0]._check(rc, "l5dh_merge_all")
         res = []

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import threading
 import time
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -128,37 +129,55 @@ class StatEngine:
         it.  Tunables set on the old engine (HistogramEngine.set_param) are not carried over."""
         capacity = int(capacity)
         self.flush()
-        with self._lock:
+        def refuse_smaller():
             if capacity <= self.capacity:
                 raise ValueError(f"grow: capacity {capacity} is not above {self.capacity}")
+
+        with self._staging_held(first=refuse_smaller):  # every thread's adds wait until the new engine is in place
+            old = self.engine
+            new = type(old)(capacity, old.device)
+            try:
+                row_off, entries, totals = old.export_sparse(first=0, count=self._next, reset=True)
+                new.import_sparse(row_off, entries, totals, first=0)
+            except Exception:
+                new.close()
+                raise
+            self.engine, self.capacity = new, int(new.max_series)
+            if self.le_cuts is not None:
+                self.le_buckets, self.le_sums = self._more_rows(self.le_buckets), self._more_rows(self.le_sums)
+            if self.quantile_q is not None:
+                self.quantile_values = self._more_rows(self.quantile_values)
+            old.close()
+
+    @contextmanager
+    def _staging_held(self, first=None):
+        """Every thread's staging lock held and its batch flushed: self._lock (held
+        throughout: a thread's first add, which registers its batch, waits too), then each
+        batch's lock in list order.  No add can fall between the engine calls made inside.
+        ``first`` runs under self._lock alone, before any staging lock is taken (a refusal)."""
+        with self._lock:
+            if first is not None:
+                first()
             bufs = list(self._buffers)
-            for st in bufs:  # every thread's adds wait until the new engine is in place
+            for st in bufs:
                 st.lock.acquire()
             try:
                 for st in bufs:
                     self._flush_locked(st)
-                old = self.engine
-                new = type(old)(capacity, old.device)
-                try:
-                    row_off, entries, totals = old.export_sparse(first=0, count=self._next, reset=True)
-                    new.import_sparse(row_off, entries, totals, first=0)
-                except Exception:
-                    new.close()
-                    raise
-                self.engine, self.capacity = new, int(new.max_series)
-                if self.le_cuts is not None:
-                    K1 = self.le_buckets.shape[1]
-                    more = self.capacity - self.le_buckets.shape[0]
-                    self.le_buckets = np.concatenate([self.le_buckets, np.zeros((more, K1), np.uint64)])
-                    self.le_sums = np.concatenate([self.le_sums, np.zeros(more, np.int64)])
-                if self.quantile_q is not None:
-                    more = self.capacity - self.quantile_values.shape[0]
-                    self.quantile_values = np.concatenate(
-                        [self.quantile_values, np.zeros((more, self.quantile_q.size), np.int64)])
-                old.close()
+                yield
             finally:
                 for st in bufs:
                     st.lock.release()
+
+    def _more_rows(self, a: np.ndarray) -> np.ndarray:
+        """A per-series side array extended with zero rows to the capacity."""
+        return np.concatenate([a, np.zeros((self.capacity - a.shape[0],) + a.shape[1:], a.dtype)])
+
+    def _start_le(self, cuts: np.ndarray, labels: np.ndarray) -> None:
+        """The lifetime ``le`` counters of these cuts, all zero."""
+        self.le_cuts, self.le_labels = cuts, labels
+        self.le_buckets = np.zeros((self.capacity, len(cuts) + 1), np.uint64)
+        self.le_sums = np.zeros(self.capacity, np.int64)
 
     def checkpoint(self, reset: bool = False) -> Dict[str, np.ndarray]:
         """The open interval and the registry as numpy arrays (np.savez takes the dict as it
@@ -207,9 +226,7 @@ class StatEngine:
             self._free = [int(x) for x in np.asarray(ckpt["free"]).reshape(-1)]
             cuts = np.asarray(ckpt["le_cuts"], np.uint32).reshape(-1)
             if cuts.size:
-                self.le_cuts, self.le_labels = cuts.copy(), np.asarray(ckpt["le_labels"], np.int64).reshape(-1).copy()
-                self.le_buckets = np.zeros((self.capacity, cuts.size + 1), np.uint64)
-                self.le_sums = np.zeros(self.capacity, np.int64)
+                self._start_le(cuts.copy(), np.asarray(ckpt["le_labels"], np.int64).reshape(-1).copy())
                 self.le_buckets[:n] = np.asarray(ckpt["le_buckets"], np.uint64).reshape(n, cuts.size + 1)
                 self.le_sums[:n] = np.asarray(ckpt["le_sums"], np.int64).reshape(-1)
             qs = np.asarray(ckpt["quantile_q"], np.float64).reshape(-1) if "quantile_q" in ckpt else np.zeros(0)
@@ -304,9 +321,7 @@ class StatEngine:
         cuts, labels = self.engine.le_cuts(bounds)
         if not 1 <= len(cuts) <= 64:
             raise ValueError(f"enable_le: {len(cuts)} distinct cuts, 1..64 are supported")
-        self.le_cuts, self.le_labels = cuts, labels
-        self.le_buckets = np.zeros((self.capacity, len(cuts) + 1), np.uint64)
-        self.le_sums = np.zeros(self.capacity, np.int64)
+        self._start_le(cuts, labels)
 
     def snapshot_all_le(self, reset: bool = True) -> np.ndarray:
         """snapshot_all plus the interval's cumulative buckets, from ONE engine call that
@@ -359,20 +374,10 @@ class StatEngine:
             self.quantile_values, summaries = self.engine.quantiles(
                 self.quantile_q, first=0, count=self.capacity, reset=reset, with_series=True)
             return summaries
-        with self._lock:  # (held throughout: a thread's first add, which registers its batch, waits too)
-            bufs = list(self._buffers)
-            for st in bufs:
-                st.lock.acquire()
-            try:
-                for st in bufs:
-                    self._flush_locked(st)
-                self.quantile_values = self.engine.quantiles(self.quantile_q, first=0, count=self.capacity,
-                                                             reset=False)
-                return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True,
-                                             with_series=True, accumulate_into=(self.le_buckets, self.le_sums))[2]
-            finally:
-                for st in bufs:
-                    st.lock.release()
+        with self._staging_held():
+            self.quantile_values = self.engine.quantiles(self.quantile_q, first=0, count=self.capacity, reset=False)
+            return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True,
+                                         with_series=True, accumulate_into=(self.le_buckets, self.le_sums))[2]
 
 
 class _Staging:
@@ -620,8 +625,14 @@ def snapshot_histograms(tree: MetricsTree, engine: StatEngine) -> int:
     """Batched AdminMetricsExportTelemeter.snapshotHistograms (:154-162): one fused
     GPU snapshot + reset of every series, then each Stat's snapshottedSummary is set.
     Returns the number of Stats updated."""
+    return _set_snapshots(tree, engine.snapshot_all)
+
+
+def _set_snapshots(tree: MetricsTree, snapshot_all) -> int:
+    """One resetting snapshot of every series (a StatEngine.snapshot_all*), then each
+    Stat's snapshottedSummary and reset time are set from it."""
     now = time.time()
-    summaries = engine.snapshot_all(reset=True)
+    summaries = snapshot_all(reset=True)
     n = 0
     for _, t in tree.walk():
         m = t.metric
@@ -635,30 +646,14 @@ def snapshot_histograms_le(tree: MetricsTree, engine: StatEngine) -> int:
     """snapshot_histograms plus the cumulative `le` buckets: the same fused snapshot +
     reset, whose interval is also added to the engine's lifetime bucket counters
     (StatEngine.enable_le) by the same engine call.  Returns the number of Stats updated."""
-    now = time.time()
-    summaries = engine.snapshot_all_le(reset=True)
-    n = 0
-    for _, t in tree.walk():
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
-            n += 1
-    return n
+    return _set_snapshots(tree, engine.snapshot_all_le)
 
 
 def snapshot_histograms_quantiles(tree: MetricsTree, engine: StatEngine) -> int:
     """snapshot_histograms plus the configured quantiles (StatEngine.enable_quantiles) of
     the same interval -- and, with enable_le, the lifetime `le` counters fed by it.  Returns
     the number of Stats updated."""
-    now = time.time()
-    summaries = engine.snapshot_all_quantiles(reset=True)
-    n = 0
-    for _, t in tree.walk():
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
-            n += 1
-    return n
+    return _set_snapshots(tree, engine.snapshot_all_quantiles)
 
 
 def top_stats(tree: MetricsTree, engine: StatEngine, k: int, by="p99", order: str = "largest", min_count: int = 1,
