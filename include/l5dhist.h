@@ -396,10 +396,16 @@ int l5dh_import_sparse(l5dh_ctx* ctx, const uint32_t* series, uint32_t first, si
  * prints as 2.82879384806159008E17).  out receives *len characters, no terminator.
  * l5dh_format_double handles +-0.0, NaN, +-Infinity and finite 2^-64 <= |x| < 2^64 --
  * everything sum / count of two int64 can be; any other value is -ERANGE (*len = 0): it
- * is never printed wrongly.  A null out or len is -EINVAL. */
+ * is never printed wrongly.  A null out or len is -EINVAL.
+ * l5dh_format_float is Float.toString of JDK 8 (the same digit loop with the float's 24
+ * significant bits, fewer for a subnormal) and handles every float: the formatter's
+ * 192-bit integer covers the whole float range.  It keeps the contract all the same: a
+ * value it could not print exactly would be -ERANGE (*len = 0), never a wrong text. */
 #define L5DH_DOUBLE_CHARS 26
+#define L5DH_FLOAT_CHARS 16
 #define L5DH_LONG_CHARS 20
 int l5dh_format_double(double x, char* out /* >= L5DH_DOUBLE_CHARS */, size_t* len);
+int l5dh_format_float(float x, char* out /* >= L5DH_FLOAT_CHARS */, size_t* len);
 int l5dh_format_long(int64_t v, char* out /* >= L5DH_LONG_CHARS */, size_t* len);
 int l5dh_format_ulong(uint64_t v, char* out /* >= L5DH_LONG_CHARS */, size_t* len);
 
@@ -453,6 +459,44 @@ int l5dh_render_le(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const uint6
                    uint8_t* out, size_t cap, size_t* len);
 int l5dh_render_quantiles(l5dh_ctx* ctx, const l5dh_names* names, size_t n, const int64_t* q_rows /* [nvalues][nq] */,
                           size_t nvalues, const double* q, uint32_t nq, uint8_t* out, size_t cap, size_t* len);
+
+/* A whole scrape on the device: the flat compact /admin/metrics.json document and the
+ * counter and gauge lines of the Prometheus exposition.  A row has a kind, kinds[j], and
+ * each kind its own value array; index[j] (index == NULL: j) counts within the row's kind:
+ *   L5DH_KIND_COUNTER  counters[index[j]]   int64, printed as l5dh_format_long
+ *   L5DH_KIND_GAUGE    gauges[index[j]]     float, printed as l5dh_format_float
+ *   L5DH_KIND_STAT     summaries[index[j]]  l5dh_render_json only
+ *
+ * l5dh_render_json writes one JSON object, byte for byte what jackson writes for
+ * AdminMetricsExportTelemeter's flat compact form: `{`, per row its entries
+ * `"<key><sfx>":<number>` separated by `,`, `}`.  key is the name already escaped as
+ * JsonGenerator.writeFieldName escapes it (UTF-8, without the quotes).  There is no label
+ * text: names->lab_off and names->lab_bytes are not read and may be NULL.  A counter and a
+ * gauge have one entry (sfx empty); a non-finite gauge is quoted ("NaN", "Infinity",
+ * "-Infinity").  A stat always has `.count`, and only when count > 0 also .max .min .p50
+ * .p90 .p95 .p99 .p9990 .p9999 .sum (longs) and .avg (l5dh_format_double, quoted when
+ * non-finite), in that order.  Without any entry (n == 0) the document is `{}`.
+ * l5dh_render_scalars writes one line `key[{inner}] <value>\n` per row, the line grammar of
+ * the calls above; a gauge is never quoted here.  n == 0 writes nothing.
+ *
+ * The contract is that of the render calls above: host or device memory for every data
+ * pointer, *len the exact length, out == NULL a size query, cap < *len -ERANGE with nothing
+ * written, no engine state read.  A value array may be NULL only with a count of 0; a
+ * non-null count with a null array, a null names, key_off or kinds (n > 0) and, for
+ * l5dh_render_scalars, a null lab_off are -EINVAL.  Found on the device, l5dh_last_error
+ * naming the first such row: a kind that is none of the above, or L5DH_KIND_STAT in
+ * l5dh_render_scalars (-EINVAL); index[j] >= the count of the row's kind, which a row of a
+ * kind without values always is (-EINVAL); offsets that descend, a key above 2^25 bytes
+ * (-EINVAL); an avg outside l5dh_format_double's domain (-ERANGE). */
+#define L5DH_KIND_COUNTER 0
+#define L5DH_KIND_GAUGE 1
+#define L5DH_KIND_STAT 2
+int l5dh_render_json(l5dh_ctx* ctx, const l5dh_names* names, const uint8_t* kinds /* [n] */, size_t n,
+                     const l5dh_summary* summaries, size_t nsummaries, const int64_t* counters, size_t ncounters,
+                     const float* gauges, size_t ngauges, uint8_t* out, size_t cap, size_t* len);
+int l5dh_render_scalars(l5dh_ctx* ctx, const l5dh_names* names, const uint8_t* kinds /* [n] */, size_t n,
+                        const int64_t* counters, size_t ncounters, const float* gauges, size_t ngauges, uint8_t* out,
+                        size_t cap, size_t* len);
 
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:

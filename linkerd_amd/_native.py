@@ -45,6 +45,8 @@ MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
 LE_MAX = 64  # L5DH_LE_MAX
 Q_MAX = 64  # L5DH_Q_MAX
 DOUBLE_CHARS = 26  # L5DH_DOUBLE_CHARS
+FLOAT_CHARS = 16  # L5DH_FLOAT_CHARS
+KIND_COUNTER, KIND_GAUGE, KIND_STAT = 0, 1, 2  # L5DH_KIND_*: a row's kind in render_json / render_scalars
 LONG_CHARS = 20  # L5DH_LONG_CHARS
 
 # top-k selection (l5dh_top, l5dh_top_summaries; the kernels' constants: csrc/l5dh_top.hpp)
@@ -114,6 +116,7 @@ SIGNATURES = {
                                       _vp, _c.c_int]),
     "l5dh_import_sparse": (_c.c_int, [_vp, _vp, _c.c_uint32, _c.c_size_t, _vp, _vp, _vp]),
     "l5dh_format_double": (_c.c_int, [_c.c_double, _vp, _c.POINTER(_c.c_size_t)]),
+    "l5dh_format_float": (_c.c_int, [_c.c_float, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_long": (_c.c_int, [_c.c_int64, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_ulong": (_c.c_int, [_c.c_uint64, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_render_summaries": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t,
@@ -122,6 +125,10 @@ SIGNATURES = {
                                   _c.POINTER(_c.c_size_t)]),
     "l5dh_render_quantiles": (_c.c_int, [_vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_uint32, _vp, _c.c_size_t,
                                          _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_json": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t,
+                                    _vp, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_scalars": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp,
+                                       _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

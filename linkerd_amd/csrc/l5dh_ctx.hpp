@@ -157,6 +157,7 @@ struct l5dh_ctx {
   // the device renderer (l5dh_render.hip): staged names, values and output, the passes' scratch
   DevBuf rd_index, rd_koff, rd_kbytes, rd_loff, rd_lbytes, rd_vals, rd_sums, rd_le, rd_out;
   DevBuf rd_len, rd_offs, rd_avg, rd_flags, rd_tmp;
+  DevBuf rd_kinds, rd_counters, rd_gauges;  // the JSON and scalar blocks' staged kinds and values
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params

@@ -1,6 +1,6 @@
 // l5dh_fmt.hpp -- Java number texts for host and device: Long.toString, the unsigned
-// 64-bit decimal, and Double.toString as JDK 8 prints it (sun.misc.FloatingDecimal:
-// BinaryToASCIIBuffer.dtoa + getChars).  A port of linkerd_amd/javafmt.py, which restates
+// 64-bit decimal, and Double.toString / Float.toString as JDK 8 prints them
+// (sun.misc.FloatingDecimal: BinaryToASCIIBuffer.dtoa + getChars).  A port of linkerd_amd/javafmt.py, which restates
 // that algorithm and is pinned by raw JDK-8 texts (tests/test_javafmt.py); the names
 // follow that module.  Plain C++ when __HIPCC__ is absent.
 //
@@ -25,6 +25,22 @@
 // 2 B - 10 S stay below 2^132.  (javafmt's own B, 10 S and M 10^18 over 38 700 sampled
 // doubles of the domain reach 110 bits.)  192 bits leave 60 bits of margin; a carry or a
 // shift out of them raises the overflow mark, which ends in FMT_RANGE.
+//
+// Domain of format_float: every float.  The same 192 bits cover the whole float range
+// (f is the float's fraction widened to the double layout, nFractBits <= 24, and
+// nSignificantBits = 24, or fewer for a subnormal):
+//   x >= 1:  B5 = 0, B = x 2^nTinyBits is x itself (< 2^128) or f (< 2^24); S = 10^S5 with
+//            S5 <= 38, so S < 2^127 and 10 S < 2^131.  Shifted up by -M2 <= 25 only when
+//            nTinyBits > 0, i.e. x < 2^24: B < 2^50.
+//   x < 1:   B5 = -decExp <= 46 (2^-149 = 1.4E-45), 5^46 < 2^107, and after the common power
+//            of two is dropped B2 = 0, then the shift -M2 = nSignificantBits + 1 - nFractBits
+//            <= 25: B < 2^24 2^107 2^25 = 2^156.  (With B / S in [0.1, 10) and S = 2^S2,
+//            S2 <= 149 - B5 + 25, the values met are far smaller: S2 = 112 at FLT_MIN, 106 at
+//            the least subnormal.)
+// As above 10 S <= 100 B and M, B + M, 2 B - 10 S stay within 12 bits of B: below 2^168.
+// So for a float (dtoa<true>) 5^k is taken beyond the 27 powers that fit a word
+// (Big::mul_pow5, n5bits' 3 k as the JDK estimates it); format_double (dtoa<false>) keeps
+// its bounds and its code.  The overflow mark still ends in FMT_RANGE.
 #pragma once
 
 #include <stddef.h>
@@ -33,14 +49,18 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define L5DH_HD __host__ __device__ inline
+// (a kernel's formatter stays part of the kernel however many kernels format: no call, no stack)
+#define L5DH_HD_FLAT __host__ __device__ __forceinline__
 #else
 #define L5DH_HD inline
+#define L5DH_HD_FLAT inline
 #endif
 
 namespace l5dh {
 namespace fmt {
 
 constexpr int DOUBLE_CHARS = 26;  // = L5DH_DOUBLE_CHARS (FloatingDecimal's own buffer)
+constexpr int FLOAT_CHARS = 16;   // = L5DH_FLOAT_CHARS: "-1.17549435E-38" is the longest, 15
 constexpr int LONG_CHARS = 20;    // = L5DH_LONG_CHARS: "-9223372036854775808", "18446744073709551615"
 constexpr int FMT_RANGE = -1;     // outside the domain
 
@@ -92,11 +112,20 @@ L5DH_HD uint64_t pow5(int k) {  // k < N_POW5
   return p;
 }
 
-L5DH_HD int n5bits(int k) { return bit_length(pow5(k)); }  // N_5_BITS[k]
+constexpr int MAX_POW5 = 47;    // 5^k of the big form: a float needs k <= 46 (5^47 < 2^110)
 
-// INSIGNIFICANT_DIGITS[p2] for p2 < 16, a nibble each: 0 0 0 0 1 1 1 2 2 2 3 3 3 3 4 4.  A
-// double on the exact-long path has binExp <= 62, so p2 = binExp - 54 <= 8.
-L5DH_HD int insignificant_digits(int p2) { return (int)((0x4433332221110000ull >> (4 * p2)) & 15ull); }
+// N_5_BITS[k]; Wide: past the table the JDK's own estimate 3 k (>= 81: the big form)
+template <bool Wide>
+L5DH_HD int n5bits(int k) { return !Wide || k < N_POW5 ? bit_length(pow5(k)) : 3 * k; }
+
+// INSIGNIFICANT_DIGITS[p2].  On the exact-long path binExp <= 62, so p2 = binExp - 54 <= 8
+// for a double: the table's first 16 entries, a nibble each (0 0 0 0 1 1 1 2 2 2 3 3 3 3 4
+// 4).  For a float (Wide) p2 = binExp - 25 <= 37: the table is floor(p2 log10 2) for p2 < 63,
+// taken as 1233 / 4096.
+template <bool Wide>
+L5DH_HD int insignificant_digits(int p2) {
+  return Wide ? (p2 * 1233) >> 12 : (int)((0x4433332221110000ull >> (4 * p2)) & 15ull);
+}
 
 // floor((d2 - 1.5) 0.289529654 + 0.176091259 + binExp log10(2)), d2 in [1, 2): each step
 // rounded on its own (no contraction), in javafmt's order.
@@ -169,7 +198,7 @@ struct Big {
     }
     ovf = ovf || carry != 0ull;
   }
-  L5DH_HD void mul_pow5(int k) {  // 5^13 < 2^32
+  L5DH_HD void mul_pow5(int k) {  // 5^13 < 2^32; any k >= 0
     for (; k >= 13; k -= 13) mul(1220703125u);
     mul((uint32_t)pow5(k));
   }
@@ -222,10 +251,13 @@ struct Big {
 // A word of the 32-bit (narrow) or 64-bit form, read as the signed value the JDK compares.
 L5DH_HD int64_t sw(bool narrow, uint64_t v) { return narrow ? (int64_t)(int32_t)(uint32_t)v : (int64_t)v; }
 
-// FloatingDecimal.BinaryToASCIIBuffer.dtoa with isCompatibleFormat = true, for a normal
-// double: fract_bits has FRACT_HOB set, n_significant_bits = 53.
-L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, Digits& out) {
-  const int n_significant_bits = EXP_SHIFT + 1;
+// FloatingDecimal.BinaryToASCIIBuffer.dtoa with isCompatibleFormat = true: fract_bits in
+// the double layout with FRACT_HOB set; n_significant_bits = 53 for a double, 24 for a
+// float, fewer for a float's subnormal.  Wide (the float's range): 5^k is taken up to
+// MAX_POW5; else, as a double of format_double's domain needs, only while it fits a word.
+template <bool Wide>
+L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, int n_sig, Digits& out) {
+  const int n_significant_bits = Wide ? n_sig : EXP_SHIFT + 1;  // (a double's is a constant)
   const int tail_zeros = __builtin_ctzll(fract_bits);
   const int n_fract_bits = EXP_SHIFT + 1 - tail_zeros;
   const int n_tiny_bits = n_fract_bits - bin_exp - 1 > 0 ? n_fract_bits - bin_exp - 1 : 0;
@@ -235,7 +267,7 @@ L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, Digits& out) {
     int insignificant = 0;
     if (bin_exp > n_significant_bits) {
       const int p2 = bin_exp - n_significant_bits - 1;
-      insignificant = p2 > 1 ? insignificant_digits(p2) : 0;
+      insignificant = p2 > 1 ? insignificant_digits<Wide>(p2) : 0;
     }
     uint64_t lv = bin_exp >= EXP_SHIFT ? fract_bits << (bin_exp - EXP_SHIFT) : fract_bits >> (EXP_SHIFT - bin_exp);
     int dec_exponent = 0;
@@ -262,7 +294,8 @@ L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, Digits& out) {
   int S2 = S5 + n_tiny_bits;
   const int M5 = B5;
   int M2 = B2 - n_significant_bits;
-  if (B5 >= N_POW5 - 1 || S5 + 1 >= N_POW5) return false;  // (outside the domain: 5^k no longer fits a word)
+  // (outside the domain: 5^k leaves the table, or a word)
+  if (Wide ? (B5 + 1 > MAX_POW5 || S5 + 1 > MAX_POW5) : (B5 >= N_POW5 - 1 || S5 + 1 >= N_POW5)) return false;
   fract_bits >>= tail_zeros;
   B2 -= n_fract_bits - 1;
   const int common2 = B2 < S2 ? B2 : S2;
@@ -276,8 +309,8 @@ L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, Digits& out) {
     M2 = 0;
   }
   if (B2 < 0 || S2 < 0) return false;  // (never for a double of the domain)
-  const int Bbits = n_fract_bits + B2 + n5bits(B5);
-  const int tenSbits = S2 + 1 + n5bits(S5 + 1);
+  const int Bbits = n_fract_bits + B2 + n5bits<Wide>(B5);
+  const int tenSbits = S2 + 1 + n5bits<Wide>(S5 + 1);
   bool low, high;
   int low_digit_difference;  // its sign only
   if (Bbits < 64 && tenSbits < 64) {
@@ -316,7 +349,8 @@ L5DH_HD bool dtoa(int bin_exp, uint64_t fract_bits, Digits& out) {
     low_digit_difference = ldd > 0 ? 1 : (ldd < 0 ? -1 : 0);
   } else {
     // FDBigInteger arithmetic (exact); note the `>=` in the high test
-    Big Sval(pow5(S5)), Bval(fract_bits), Mval(1ull), tenSval(1ull);
+    Big Sval(Wide ? 1ull : pow5(S5)), Bval(fract_bits), Mval(1ull), tenSval(1ull);
+    if (Wide) Sval.mul_pow5(S5);
     Sval.shl(S2);
     Bval.mul_pow5(B5);
     Bval.shl(B2);
@@ -419,7 +453,7 @@ L5DH_HD int put_text(const char* s, Ch* out) {
 // java.lang.Double.toString(double) on JDK 8 into out[DOUBLE_CHARS]: the length, or
 // FMT_RANGE outside the domain.
 template <class Ch>
-L5DH_HD int format_double(double x, Ch* out) {
+L5DH_HD_FLAT int format_double(double x, Ch* out) {
   uint64_t bits;
   __builtin_memcpy(&bits, &x, 8);
   const bool neg = (bits >> 63) != 0ull;
@@ -430,8 +464,38 @@ L5DH_HD int format_double(double x, Ch* out) {
   bin_exp -= EXP_BIAS;
   if (bin_exp < -64 || bin_exp > 63) return FMT_RANGE;
   Digits d;
-  if (!dtoa(bin_exp, fract | FRACT_HOB, d)) return FMT_RANGE;
+  if (!dtoa<false>(bin_exp, fract | FRACT_HOB, EXP_SHIFT + 1, d)) return FMT_RANGE;
   if (d.n + 7 > DOUBLE_CHARS) return FMT_RANGE;  // (sign, `.`, `E`, three exponent characters, `0.00`)
+  return get_chars(neg, d, out);
+}
+
+// java.lang.Float.toString(float) on JDK 8 into out[FLOAT_CHARS]: the float widened to the
+// double layout (fraction left-aligned to bit 52, a subnormal normalised and its
+// significant bits counted), then the same dtoa and getChars.  The length, or FMT_RANGE.
+template <class Ch>
+L5DH_HD_FLAT int format_float(float x, Ch* out) {
+  constexpr int F_FRAC = 23, F_BIAS = 127;
+  uint32_t bits;
+  __builtin_memcpy(&bits, &x, 4);
+  const bool neg = (bits >> 31) != 0u;
+  int bin_exp = (int)((bits >> F_FRAC) & 0xFFu);
+  uint64_t fract = (uint64_t)(bits & ((1u << F_FRAC) - 1u)) << (EXP_SHIFT - F_FRAC);
+  if (bin_exp == 0xFF) return fract ? put_text("NaN", out) : put_text(neg ? "-Infinity" : "Infinity", out);
+  int n_sig = F_FRAC + 1;
+  if (bin_exp == 0) {
+    if (!fract) return put_text(neg ? "-0.0" : "0.0", out);
+    const int lead = __builtin_clzll(fract);
+    const int shift = lead - (63 - EXP_SHIFT);
+    fract <<= shift;  // (its leading one arrives at FRACT_HOB)
+    bin_exp = 1 - shift;
+    n_sig = 64 - lead - (EXP_SHIFT - F_FRAC);
+  } else {
+    fract |= FRACT_HOB;
+  }
+  bin_exp -= F_BIAS;
+  Digits d;
+  if (!dtoa<true>(bin_exp, fract, n_sig, d)) return FMT_RANGE;
+  if (d.n + 7 > FLOAT_CHARS) return FMT_RANGE;  // (nine digits at most, beside sign, `.`, `E-38` or `0.00`)
   return get_chars(neg, d, out);
 }
 

@@ -434,6 +434,8 @@ int rd_stage_bytes(l5dh_ctx* c, const uint8_t*& bytes, const uint64_t* off, size
 // The findings of the passes, in the order the header lists them.
 int rd_findings(l5dh_ctx* c, const uint32_t* f) {
   const uint32_t none = 0xFFFFFFFFu;
+  if (f[RF_KIND] != none)
+    return fail(c, -EINVAL, "render: the kind of row " + std::to_string(f[RF_KIND]) + " is not one the call prints");
   if (f[RF_BADIDX] != none)
     return fail(c, -EINVAL, "render: index of row " + std::to_string(f[RF_BADIDX]) + " is not < nvalues");
   if (f[RF_BADOFF] != none)
@@ -442,23 +444,27 @@ int rd_findings(l5dh_ctx* c, const uint32_t* f) {
     return fail(c, -EINVAL, "render: key and label text of row " + std::to_string(f[RF_LONG]) + " exceed 2^25 bytes");
   if (f[RF_RANGE] != none)
     return fail(c, -ERANGE,
-                "render: avg of row " + std::to_string(f[RF_RANGE]) + " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
+                "render: avg or gauge of row " + std::to_string(f[RF_RANGE]) +
+                    " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
   if (f[RF_MISMATCH] != none)
     return fail(c, -EIO, "internal: the render passes disagree on the length of row " + std::to_string(f[RF_MISMATCH]));
   return 0;
 }
 
 // The passes over n > 0 rows; rows holds device pointers (the caller staged the values).
-// The caller holds the lock and has checked the arguments.
+// The caller holds the lock and has checked the arguments.  braces: the rows' text is the
+// inside of one JSON object -- it goes from out + 1, `{` goes to out[0] and `}` over the
+// last entry's comma (no entry at all: `{}`), and names' label text is not read.
 template <class Rows>
 int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, const Rows& rows, uint8_t* out, size_t cap,
-              size_t* len) {
+              size_t* len, bool braces = false) {
   int r;
-  RenderNames nm{names->index, names->key_off, names->key_bytes, names->lab_off, names->lab_bytes};
+  RenderNames nm{names->index, names->key_off, names->key_bytes, braces ? nullptr : names->lab_off,
+                 braces ? nullptr : names->lab_bytes};
   {
     KTimer kt(c, L5DH_K_COPY);
     if ((r = rd_stage_bytes(c, nm.key_bytes, names->key_off, n, c->rd_kbytes)) ||
-        (r = rd_stage_bytes(c, nm.lab_bytes, names->lab_off, n, c->rd_lbytes)) ||
+        (nm.lab_off && (r = rd_stage_bytes(c, nm.lab_bytes, names->lab_off, n, c->rd_lbytes))) ||
         (r = stage_in(c, nm.index, n, 4, c->rd_index)) || (r = stage_in(c, nm.key_off, n + 1, 8, c->rd_koff)) ||
         (r = stage_in(c, nm.lab_off, n + 1, 8, c->rd_loff)))
       return r;
@@ -482,6 +488,8 @@ int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, co
   HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
   if ((r = sync_stream(c)) || (r = rd_findings(c, hf))) return r;
+  const uint64_t rows_total = total;
+  if (braces) total = total ? total + 1 : 2;
   if (len) *len = (size_t)total;
   if (!out) return 0;  // a size query
   if (cap < total)
@@ -490,7 +498,11 @@ int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, co
   if ((r = o.begin(c, out, (size_t)total, c->rd_out, 1))) return r;
   {
     KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, render_write(nm, (uint32_t)n, rows, offs, o.dev, flags, c->stream));
+    if (rows_total) HIPCHK(c, render_write(nm, (uint32_t)n, rows, offs, o.dev + (braces ? 1 : 0), flags, c->stream));
+    if (braces) {
+      HIPCHK(c, hipMemsetAsync(o.dev, '{', 1, c->stream));
+      HIPCHK(c, hipMemsetAsync(o.dev + total - 1, '}', 1, c->stream));
+    }
   }
   {
     KTimer kt(c, L5DH_K_COPY);
@@ -508,6 +520,36 @@ int rd_check(l5dh_ctx* c, const l5dh_names* names, size_t n, const void* values,
   if (n == 0) return 1;
   if (nvalues == 0 || !values) return fail(c, -EINVAL, "render: no values for the rows");
   if (n > 0xFFFFFFF0ull || nvalues > 0xFFFFFFFFull) return fail(c, -EINVAL, "render: more than 2^32 - 16 rows");
+  return 0;
+}
+
+// The arguments the JSON and the scalar call share, and their staged values.  0: go on;
+// 1: n == 0; negative: an error.
+int rd_kind_check(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kinds, size_t n, bool labels, KindRows& k,
+                  size_t nsummaries, size_t ncounters, size_t ngauges, size_t* len) {
+  if (len) *len = 0;
+  if (!names || !names->key_off || (labels && !names->lab_off))
+    return fail(c, -EINVAL, labels ? "render: null names, key_off or lab_off" : "render: null names or key_off");
+  if ((nsummaries && !k.summaries) || (ncounters && !k.counters) || (ngauges && !k.gauges))
+    return fail(c, -EINVAL, "render: a null value array with a count above 0");
+  if (n == 0) return 1;
+  if (!kinds) return fail(c, -EINVAL, "render: null kinds");
+  if (n > 0xFFFFFFF0ull || nsummaries > 0xFFFFFFFFull || ncounters > 0xFFFFFFFFull || ngauges > 0xFFFFFFFFull)
+    return fail(c, -EINVAL, "render: more than 2^32 - 16 rows");
+  k.kinds = kinds;
+  k.nsummaries = (uint32_t)nsummaries;
+  k.ncounters = (uint32_t)ncounters;
+  k.ngauges = (uint32_t)ngauges;
+  int r;
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = stage_in(c, k.kinds, n, 1, c->rd_kinds)) || (r = stage_in(c, k.summaries, nsummaries, 8, c->rd_vals)) ||
+        (r = stage_in(c, k.counters, ncounters, 8, c->rd_counters)) ||
+        (r = stage_in(c, k.gauges, ngauges, 4, c->rd_gauges)))
+      return r;
+  }
+  if ((r = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT))) return r;
+  k.slot = c->rd_avg.as<uint8_t>();
   return 0;
 }
 
@@ -664,6 +706,13 @@ int l5dh_format_double(double x, char* out, size_t* len) {
   return n < 0 ? -ERANGE : 0;
 }
 
+int l5dh_format_float(float x, char* out, size_t* len) {
+  if (!out || !len) return -EINVAL;
+  const int n = fmt::format_float(x, out);
+  *len = n < 0 ? 0 : (size_t)n;
+  return n < 0 ? -ERANGE : 0;
+}
+
 int l5dh_format_long(int64_t v, char* out, size_t* len) {
   if (!out || !len) return -EINVAL;
   *len = (size_t)fmt::format_long(v, out);
@@ -738,6 +787,34 @@ int l5dh_render_quantiles(l5dh_ctx* c, const l5dh_names* names, size_t n, const 
   }
   // (labels lives on this frame: do_render returns only after the stream has drained)
   return do_render(c, names, n, nvalues, QuantRows{q_rows, lab, nq}, out, cap, len);
+}
+
+int l5dh_render_json(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kinds, size_t n, const l5dh_summary* summaries,
+                     size_t nsummaries, const int64_t* counters, size_t ncounters, const float* gauges, size_t ngauges,
+                     uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  KindRows k{nullptr, reinterpret_cast<const Summary88*>(summaries), counters, gauges, 0u, 0u, 0u, nullptr};
+  int r = rd_kind_check(c, names, kinds, n, false, k, nsummaries, ncounters, ngauges, len);
+  if (r < 0) return r;
+  if (r == 1) {  // the empty document
+    if (len) *len = 2;
+    if (!out) return 0;
+    if (cap < 2) return fail(c, -ERANGE, "render: the text takes 2 bytes, cap is " + std::to_string(cap));
+    HIPCHK(c, hipMemcpyAsync(out, "{}", 2, hipMemcpyDefault, c->stream));
+    return sync_stream(c);
+  }
+  return do_render(c, names, n, 0, JsonRows{k}, out, cap, len, true);
+}
+
+int l5dh_render_scalars(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kinds, size_t n, const int64_t* counters,
+                        size_t ncounters, const float* gauges, size_t ngauges, uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  KindRows k{nullptr, nullptr, counters, gauges, 0u, 0u, 0u, nullptr};
+  int r = rd_kind_check(c, names, kinds, n, true, k, 0, ncounters, ngauges, len);
+  if (r) return r < 0 ? r : 0;
+  return do_render(c, names, n, 0, ScalarRows{k}, out, cap, len);
 }
 
 }  // extern "C"

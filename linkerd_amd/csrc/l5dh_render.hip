@@ -1,14 +1,18 @@
-// l5dh_render.hip -- the Prometheus text of Stats, produced where the numbers are.
+// l5dh_render.hip -- the text of a scrape, produced where the numbers are.
 //
 // A row's block is a list of lines, each
-//     key sfx [ `{` inner [`, `] ext ev `"` `}` ] ` ` number `\n`
+//     open key sfx [ `{` inner [`, `] ext ev `"` `}` ] sep number end
 // with key / inner the row's name bytes, sfx / ext / ev small constant texts (or, for ev,
-// an `le` label or a quantile's label) and number a Java long, an unsigned 64-bit decimal or the avg's
-// Double.toString.  prometheus.py's write_metrics, write_rollup_metrics,
-// write_histogram_metrics and write_quantile_metrics print exactly these lines.
+// an `le` label or a quantile's label) and number a Java long, an unsigned 64-bit decimal or
+// a text formatted once per row (the avg's Double.toString, a gauge's Float.toString).
+// open, sep and end are the block's grammar: nothing, a space and a newline for the
+// Prometheus lines that prometheus.py's write_metrics, write_rollup_metrics,
+// write_histogram_metrics, write_quantile_metrics and write_scalar_metrics print; `"`,
+// `":` and `,` for the entries of admin_metrics.py's write_flat_json.  The number of
+// lines is the row's: a JSON stat row has one entry, or eleven when its count is above 0.
 //
-//   k_rd_len    a lane per row: checks the row (index, offsets, name length), formats its
-//               avg once into the row's 32-byte slot, and adds up the lines' lengths from
+//   k_rd_len    a lane per row: checks the row (kind, index, offsets, name length), formats
+//               its avg or gauge once into the row's 32-byte slot, and adds up the lines' lengths from
 //               the name lengths and the digit counts.
 //   (scan)      the fleet merge's exclusive u32 -> u64 scan (merge_count).
 //   k_rd_write  a wave per row (one-wave workgroups striding over the rows).  Lane t lays
@@ -52,15 +56,31 @@ __device__ __forceinline__ uint32_t num_len(const Line& L) {
 }
 __device__ __forceinline__ uint32_t ev_len(const Line& L) { return L.ev ? L.ev_n : (uint32_t)fmt::long_digits(L.ev_num); }
 
-// Bytes of the line up to its inner text (key, sfx, `{`) and in all.
+// A block's grammar: what precedes the key (open_n bytes: none or one), what stands between
+// the name part and the number (sep_n bytes: one or two), what ends the line, and whether
+// a row has label text at all (false: lab_off and lab_bytes are never read).
+struct PromGrammar {
+  static constexpr bool labels = true;
+  static constexpr uint32_t open_n = 0u, sep_n = 1u;
+  static constexpr uint8_t open = 0, sep0 = ' ', sep1 = 0, end = '\n';
+};
+struct JsonGrammar {
+  static constexpr bool labels = false;
+  static constexpr uint32_t open_n = 1u, sep_n = 2u;
+  static constexpr uint8_t open = '"', sep0 = '"', sep1 = ':', end = ',';
+};
+
+// Bytes of the line up to its inner text (open, key, sfx, `{`) and in all.
+template <class G>
 __device__ __forceinline__ uint32_t line_head(uint32_t klen, uint32_t ilen, const Line& L) {
-  return klen + L.sfx_n + ((ilen || L.ext_n) ? 1u : 0u);
+  return G::open_n + klen + L.sfx_n + ((ilen || L.ext_n) ? 1u : 0u);
 }
+template <class G>
 __device__ __forceinline__ uint32_t line_len(uint32_t klen, uint32_t ilen, const Line& L) {
-  uint32_t n = line_head(klen, ilen, L) + ilen;
+  uint32_t n = line_head<G>(klen, ilen, L) + ilen;
   if (L.ext_n) n += (ilen ? 2u : 0u) + L.ext_n + ev_len(L) + 1u;  // [`, `] ext ev `"`
   if (ilen || L.ext_n) n += 1u;                                    // `}`
-  return n + 1u + num_len(L) + 1u;                                 // ` ` number `\n`
+  return n + G::sep_n + num_len(L) + 1u;                           // sep number end
 }
 
 template <class S>
@@ -71,8 +91,10 @@ __device__ __forceinline__ uint32_t put(uint8_t* dst, uint32_t p, const S* s, ui
 
 // The lane's own pieces of its line at dst + pos: everything but key and inner.  Writes
 // inside [pos, pos + line_len) only, and ends exactly there.
+template <class G>
 __device__ __forceinline__ void line_write(uint8_t* dst, uint32_t pos, uint32_t klen, uint32_t ilen, const Line& L) {
-  uint32_t p = put(dst, pos + klen, L.sfx, L.sfx_n);
+  if (G::open_n) dst[pos] = G::open;
+  uint32_t p = put(dst, pos + G::open_n + klen, L.sfx, L.sfx_n);
   if (ilen || L.ext_n) dst[p++] = '{';
   p += ilen;
   if (L.ext_n) {
@@ -88,22 +110,29 @@ __device__ __forceinline__ void line_write(uint8_t* dst, uint32_t pos, uint32_t 
     dst[p++] = '"';
   }
   if (ilen || L.ext_n) dst[p++] = '}';
-  dst[p++] = ' ';
+  dst[p++] = G::sep0;
+  if (G::sep_n > 1u) dst[p++] = G::sep1;
   if (L.kind == NUM_TEXT)
     p = put(dst, p, L.text, L.text_n);
   else if (L.kind == NUM_LONG)
     p += (uint32_t)fmt::format_long((int64_t)L.v, dst + p);
   else
     p += (uint32_t)fmt::format_ulong(L.v, dst + p);
-  dst[p] = '\n';
+  dst[p] = G::end;
 }
 
-// ---- the three blocks -------------------------------------------------------------
+// ---- the blocks ---------------------------------------------------------------------
+// A block has its grammar G; kind_ok(j): row j is of a kind the call prints;
+// values(j, nvalues): the number of values the row indexes; prepare(j, idx): the length pass's own work for
+// the row (false: out of the formatter's domain); nlines(j, idx) and line(j, idx, t, L).
 // Summary: _count, _sum, _avg, then QUANTILES' eight lines (min, p50, .., p9999, max).
 struct SummaryBlock {
+  using G = PromGrammar;
   SummaryRows r;
-  __device__ __forceinline__ uint32_t nlines() const { return 11u; }
-  // The length pass's own work for row j (value idx): the avg's text.  False: out of domain.
+  __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
+  __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
+  __device__ __forceinline__ uint32_t nlines(uint32_t, uint32_t) const { return 11u; }
+  // The avg's text.
   __device__ __forceinline__ bool prepare(uint32_t j, uint32_t idx) const {
     uint8_t* slot = r.avg + (size_t)j * RENDER_AVG_SLOT;
     const int n = fmt::format_double(r.v[idx].avg, slot);
@@ -132,8 +161,11 @@ struct SummaryBlock {
 
 // Histogram: K `_hist_bucket` lines with le="<label>", the le="+Inf" line, _hist_sum, _hist_count.
 struct LeBlock {
+  using G = PromGrammar;
   LeRows r;
-  __device__ __forceinline__ uint32_t nlines() const { return r.K + 3u; }
+  __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
+  __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
+  __device__ __forceinline__ uint32_t nlines(uint32_t, uint32_t) const { return r.K + 3u; }
   __device__ __forceinline__ bool prepare(uint32_t, uint32_t) const { return true; }
   __device__ __forceinline__ void line(uint32_t, uint32_t idx, uint32_t t, Line& L) const {
     const uint32_t K = r.K;
@@ -155,8 +187,11 @@ struct LeBlock {
 // Configured quantiles: K lines with quantile="<label>", the label the quantile's
 // Double.toString -- bytes the host formatted once per call, in global memory.
 struct QuantileBlock {
+  using G = PromGrammar;
   QuantRows r;
-  __device__ __forceinline__ uint32_t nlines() const { return r.K; }
+  __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
+  __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
+  __device__ __forceinline__ uint32_t nlines(uint32_t, uint32_t) const { return r.K; }
   __device__ __forceinline__ bool prepare(uint32_t, uint32_t) const { return true; }
   __device__ __forceinline__ void line(uint32_t, uint32_t idx, uint32_t t, Line& L) const {
     const uint8_t* slot = r.labels + (size_t)t * RENDER_QLABEL_SLOT;
@@ -174,6 +209,117 @@ struct QuantileBlock {
   }
 };
 
+// What the JSON and the scalar block share: the count of a row's kind, and the row's text
+// (a gauge's Float.toString, a stat's avg) in its slot -- between quotes when `quote` and
+// the value is not finite, as jackson writes such a number.
+struct KindBlock {
+  KindRows r;
+  __device__ __forceinline__ bool kind_ok(uint32_t j, bool stats) const {
+    const uint8_t k = r.kinds[j];
+    return k == KIND_COUNTER || k == KIND_GAUGE || (stats && k == KIND_STAT);
+  }
+  __device__ __forceinline__ uint32_t values(uint32_t j) const {
+    const uint8_t k = r.kinds[j];
+    return k == KIND_COUNTER ? r.ncounters : (k == KIND_GAUGE ? r.ngauges : r.nsummaries);
+  }
+  __device__ __forceinline__ bool slot_text(uint32_t j, uint32_t idx, bool quote) const {
+    const uint8_t k = r.kinds[j];
+    if (k == KIND_COUNTER) return true;
+    uint8_t* slot = r.slot + (size_t)j * RENDER_AVG_SLOT;
+    int n;
+    bool finite;
+    if (k == KIND_GAUGE) {
+      const float x = r.gauges[idx];
+      uint32_t bits;
+      __builtin_memcpy(&bits, &x, 4);
+      finite = (bits & 0x7F800000u) != 0x7F800000u;
+      n = fmt::format_float(x, slot + 1);
+    } else {
+      const double x = r.summaries[idx].avg;
+      uint64_t bits;
+      __builtin_memcpy(&bits, &x, 8);
+      finite = (bits & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+      n = r.summaries[idx].count > 0 ? fmt::format_double(x, slot + 1) : 0;  // (printed only then)
+    }
+    // the text stands at slot + 1; a quoted one begins at slot + 0
+    static_assert(fmt::DOUBLE_CHARS + 3 <= (int)RENDER_AVG_SLOT, "text, two quotes and the length share a slot");
+    const bool q = quote && !finite && n > 0;
+    if (q) slot[0] = slot[n + 1] = '"';
+    slot[RENDER_AVG_SLOT - 2] = q ? 0 : 1;  // where the text begins
+    slot[RENDER_AVG_SLOT - 1] = (uint8_t)(n < 0 ? 0 : (q ? n + 2 : n));
+    return n >= 0;
+  }
+  __device__ __forceinline__ void slot_line(uint32_t j, Line& L) const {
+    const uint8_t* slot = r.slot + (size_t)j * RENDER_AVG_SLOT;
+    L.kind = NUM_TEXT;
+    L.v = 0ull;
+    L.text = slot + slot[RENDER_AVG_SLOT - 2];
+    L.text_n = slot[RENDER_AVG_SLOT - 1];
+  }
+  __device__ __forceinline__ void plain(Line& L) const {  // no sfx, no extra label, no number yet
+    L.sfx = "";
+    L.sfx_n = 0u;
+    L.ext = "";
+    L.ext_n = 0u;
+    L.ev = "";
+    L.ev_n = 0u;
+    L.ev_num = 0;
+    L.kind = NUM_LONG;
+    L.v = 0ull;
+    L.text = nullptr;
+    L.text_n = 0u;
+  }
+};
+
+// /admin/metrics.json, flat and compact: a counter's or a gauge's entry; a stat's `.count`
+// and, only when count > 0, STAT_FIELDS' nine longs and `.avg`.
+struct JsonBlock {
+  using G = JsonGrammar;
+  KindBlock b;
+  __device__ __forceinline__ bool kind_ok(uint32_t j) const { return b.kind_ok(j, true); }
+  __device__ __forceinline__ uint32_t values(uint32_t j, uint32_t) const { return b.values(j); }
+  __device__ __forceinline__ bool prepare(uint32_t j, uint32_t idx) const { return b.slot_text(j, idx, true); }
+  __device__ __forceinline__ uint32_t nlines(uint32_t j, uint32_t idx) const {
+    return b.r.kinds[j] == KIND_STAT && b.r.summaries[idx].count > 0 ? 11u : 1u;
+  }
+  __device__ __forceinline__ void line(uint32_t j, uint32_t idx, uint32_t t, Line& L) const {
+    b.plain(L);
+    const uint8_t k = b.r.kinds[j];
+    if (k == KIND_COUNTER) {
+      L.v = (uint64_t)b.r.counters[idx];
+    } else if (k == KIND_GAUGE) {
+      b.slot_line(j, L);
+    } else {
+      const char* sfx = ".count .max   .min   .p50   .p90   .p95   .p99   .p9990 .p9999 .sum   .avg";  // 7 bytes apart
+      L.sfx = sfx + 7u * t;
+      L.sfx_n = (uint32_t)(0x44664444446ull >> (4u * t)) & 15u;  // their lengths: 6 4 4 4 4 4 4 6 6 4 4
+      // Summary88's words: count, min, max, sum, p50, p90, p95, p99, p9990, p9999
+      const uint32_t field = t == 0 ? 0u : (t == 1 ? 2u : (t == 2 ? 1u : (t == 9 ? 3u : t + 1u)));
+      if (t == 10)
+        b.slot_line(j, L);
+      else
+        L.v = (uint64_t)reinterpret_cast<const int64_t*>(b.r.summaries + idx)[field];
+    }
+  }
+};
+
+// The counter and gauge lines of the Prometheus exposition: one line per row.
+struct ScalarBlock {
+  using G = PromGrammar;
+  KindBlock b;
+  __device__ __forceinline__ bool kind_ok(uint32_t j) const { return b.kind_ok(j, false); }
+  __device__ __forceinline__ uint32_t values(uint32_t j, uint32_t) const { return b.values(j); }
+  __device__ __forceinline__ bool prepare(uint32_t j, uint32_t idx) const { return b.slot_text(j, idx, false); }
+  __device__ __forceinline__ uint32_t nlines(uint32_t, uint32_t) const { return 1u; }
+  __device__ __forceinline__ void line(uint32_t j, uint32_t idx, uint32_t, Line& L) const {
+    b.plain(L);
+    if (b.r.kinds[j] == KIND_COUNTER)
+      L.v = (uint64_t)b.r.counters[idx];
+    else
+      b.slot_line(j, L);
+  }
+};
+
 // ---- length pass ------------------------------------------------------------------
 template <class Block>
 __global__ __launch_bounds__(256) void k_rd_len(RenderNames nm, uint32_t n, uint32_t nvalues, Block blk,
@@ -181,9 +327,14 @@ __global__ __launch_bounds__(256) void k_rd_len(RenderNames nm, uint32_t n, uint
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= n) return;
   const uint32_t idx = nm.index ? nm.index[j] : j;
-  const uint64_t k0 = nm.key_off[j], k1 = nm.key_off[j + 1], i0 = nm.lab_off[j], i1 = nm.lab_off[j + 1];
+  const uint64_t k0 = nm.key_off[j], k1 = nm.key_off[j + 1];
+  constexpr bool labels = Block::G::labels;
+  const uint64_t i0 = labels ? nm.lab_off[j] : 0ull, i1 = labels ? nm.lab_off[j + 1] : 0ull;
   bool ok = true;
-  if (idx >= nvalues) {
+  if (!blk.kind_ok(j)) {
+    atomicMin(flags + RF_KIND, j);
+    ok = false;
+  } else if (idx >= blk.values(j, nvalues)) {
     atomicMin(flags + RF_BADIDX, j);
     ok = false;
   }
@@ -200,11 +351,11 @@ __global__ __launch_bounds__(256) void k_rd_len(RenderNames nm, uint32_t n, uint
   }
   uint32_t total = 0u;
   if (ok) {
-    const uint32_t klen = (uint32_t)(k1 - k0), ilen = (uint32_t)(i1 - i0), nl = blk.nlines();
+    const uint32_t klen = (uint32_t)(k1 - k0), ilen = (uint32_t)(i1 - i0), nl = blk.nlines(j, idx);
     for (uint32_t t = 0; t < nl; ++t) {
       Line L;
       blk.line(j, idx, t, L);
-      total += line_len(klen, ilen, L);
+      total += line_len<typename Block::G>(klen, ilen, L);
     }
   }
   len[j] = total;
@@ -225,7 +376,8 @@ __device__ __forceinline__ bool build_row(uint8_t* dst, const Block& blk, uint32
                                           const uint8_t* __restrict__ key, uint32_t klen,
                                           const uint8_t* __restrict__ inner, uint32_t ilen, uint32_t rowlen,
                                           uint32_t* lpos, uint32_t* ipos, uint32_t lane) {
-  const uint32_t nl = blk.nlines();
+  using G = typename Block::G;
+  const uint32_t nl = blk.nlines(j, idx);
   // every line's place first: nothing is written before the total is known to match
   uint32_t cursor = 0u;
   for (uint32_t base = 0; base < nl; base += 64u) {  // (wave-uniform bounds)
@@ -234,12 +386,12 @@ __device__ __forceinline__ bool build_row(uint8_t* dst, const Block& blk, uint32
     uint32_t ln = 0u;
     if (t < nl) {
       blk.line(j, idx, t, L);
-      ln = line_len(klen, ilen, L);
+      ln = line_len<G>(klen, ilen, L);
     }
     const uint32_t incl = wave_incl_scan32(ln);
     if (t < nl) {
       lpos[t] = cursor + incl - ln;
-      ipos[t] = cursor + incl - ln + line_head(klen, ilen, L);
+      ipos[t] = cursor + incl - ln + line_head<G>(klen, ilen, L);
     }
     cursor += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
   }
@@ -250,12 +402,12 @@ __device__ __forceinline__ bool build_row(uint8_t* dst, const Block& blk, uint32
     if (t < nl) {
       Line L;
       blk.line(j, idx, t, L);
-      line_write(dst, lpos[t], klen, ilen, L);
+      line_write<G>(dst, lpos[t], klen, ilen, L);
     }
   }
   const uint8_t kpre = lane < klen ? key[lane] : (uint8_t)0, ipre = lane < ilen ? inner[lane] : (uint8_t)0;
   for (uint32_t t = 0; t < nl; ++t) {
-    emit(dst + lpos[t], key, klen, kpre, lane);
+    emit(dst + lpos[t] + G::open_n, key, klen, kpre, lane);
     emit(dst + ipos[t], inner, ilen, ipre, lane);
   }
   return true;
@@ -270,8 +422,9 @@ __global__ __launch_bounds__(64) void k_rd_write(RenderNames nm, uint32_t n, Blo
   const uint32_t lane = threadIdx.x;
   for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {  // (wave-uniform)
     const uint32_t idx = nm.index ? nm.index[j] : j;
-    const uint64_t k0 = nm.key_off[j], i0 = nm.lab_off[j], o0 = offs[j];
-    const uint32_t klen = (uint32_t)(nm.key_off[j + 1] - k0), ilen = (uint32_t)(nm.lab_off[j + 1] - i0);
+    constexpr bool labels = Block::G::labels;
+    const uint64_t k0 = nm.key_off[j], i0 = labels ? nm.lab_off[j] : 0ull, o0 = offs[j];
+    const uint32_t klen = (uint32_t)(nm.key_off[j + 1] - k0), ilen = labels ? (uint32_t)(nm.lab_off[j + 1] - i0) : 0u;
     const uint32_t rowlen = (uint32_t)(offs[j + 1] - o0);
     const uint8_t* key = nm.key_bytes + k0;
     const uint8_t* inner = nm.lab_bytes + i0;
@@ -334,6 +487,14 @@ hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, c
   if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
   return lengths(nm, n, nvalues, QuantileBlock{rows}, len, flags, st);
 }
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const JsonRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  return lengths(nm, n, nvalues, JsonBlock{KindBlock{rows.k}}, len, flags, st);
+}
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const ScalarRows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  return lengths(nm, n, nvalues, ScalarBlock{KindBlock{rows.k}}, len, flags, st);
+}
 hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
                         uint32_t* flags, hipStream_t st) {
   return write(nm, n, SummaryBlock{rows}, offs, out, flags, st);
@@ -348,6 +509,14 @@ hipError_t render_write(const RenderNames& nm, uint32_t n, const QuantRows& rows
                         uint32_t* flags, hipStream_t st) {
   if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
   return write(nm, n, QuantileBlock{rows}, offs, out, flags, st);
+}
+hipError_t render_write(const RenderNames& nm, uint32_t n, const JsonRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  return write(nm, n, JsonBlock{KindBlock{rows.k}}, offs, out, flags, st);
+}
+hipError_t render_write(const RenderNames& nm, uint32_t n, const ScalarRows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  return write(nm, n, ScalarBlock{KindBlock{rows.k}}, offs, out, flags, st);
 }
 
 }  // namespace l5dh

@@ -144,18 +144,22 @@ class NameTable:
     the names, none of which varies per scrape: per row the escaped metric key and the
     escaped text between the braces, as UTF-8 bytes behind n + 1 offsets, and ``index``,
     the element of the value arrays the row prints (None: the row's own number).
-    ``metrics`` (host tables of a tree) are the rows' Stats."""
+    ``metrics`` (host tables of a tree) are the rows' Stats.  ``kinds`` (None: every row a
+    Stat) is a uint8 per row, _native.KIND_COUNTER / KIND_GAUGE / KIND_STAT, for the calls
+    of linkerd_amd.render_json: ``index`` then counts within the row's kind, and
+    ``metrics`` holds the rows' metrics of any kind."""
 
-    def __init__(self, index, key_off, key_bytes, lab_off, lab_bytes, metrics=None):
+    def __init__(self, index, key_off, key_bytes, lab_off, lab_bytes, metrics=None, kinds=None):
         self.index, self.key_off, self.key_bytes = index, key_off, key_bytes
         self.lab_off, self.lab_bytes, self.metrics = lab_off, lab_bytes, metrics
+        self.kinds = kinds
 
     @property
     def n(self) -> int:
         return int(self.key_off.shape[0]) - 1
 
     @staticmethod
-    def build(keys: Sequence[str], inners: Sequence[str], index=None, metrics=None) -> "NameTable":
+    def build(keys: Sequence[str], inners: Sequence[str], index=None, metrics=None, kinds=None) -> "NameTable":
         def pack(texts):
             enc = [t.encode("utf-8") for t in texts]
             off = np.zeros(len(enc) + 1, np.uint64)
@@ -165,7 +169,9 @@ class NameTable:
         lab_off, lab_bytes = pack(inners)
         if index is not None:
             index = np.ascontiguousarray(np.asarray(index, np.int64).astype(np.uint32))
-        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics)
+        if kinds is not None:
+            kinds = np.ascontiguousarray(np.asarray(kinds, np.uint8))
+        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics, kinds)
 
     def take(self, rows) -> "NameTable":
         """The table of the given rows, in that order (a host table)."""
@@ -182,7 +188,8 @@ class NameTable:
         lab_off, lab_bytes = gather(self.lab_off, self.lab_bytes)
         index = None if self.index is None else self.index[rows]
         metrics = None if self.metrics is None else [self.metrics[int(r)] for r in rows]
-        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics)
+        kinds = None if self.kinds is None else self.kinds[rows]
+        return NameTable(index, key_off, key_bytes, lab_off, lab_bytes, metrics, kinds)
 
     def to_device(self, device: int = 0) -> "NameTable":
         """The same table in device memory (torch tensors): uploaded once, reused by
@@ -198,7 +205,7 @@ class NameTable:
             a = a.view({8: np.int64, 4: np.int32}.get(a.dtype.itemsize, np.uint8)) if a.dtype.kind == "u" else a
             return torch.from_numpy(a).to(dev)
         return NameTable(up(self.index), up(self.key_off), up(self.key_bytes), up(self.lab_off), up(self.lab_bytes),
-                         self.metrics)
+                         self.metrics, up(self.kinds))
 
 
 def stat_name_table(tree: MetricsTree) -> NameTable:
@@ -251,6 +258,45 @@ def write_scalar_metrics(tree: MetricsTree, out: List[str], prefix0: Tuple[str, 
         write_scalar_metrics(child, out, prefix1 + (name,), labels1)
 
 
+def scalar_name_table(tree: MetricsTree) -> NameTable:
+    """The name table of the counters and gauges of ``tree``, walked exactly as
+    write_scalar_metrics walks it: one row per counter or gauge in DFS order with its
+    kind, ``index`` its ordinal among the rows of its kind (the order of scalar_values)."""
+    from ._native import KIND_COUNTER, KIND_GAUGE
+    keys: List[str] = []
+    inners: List[str] = []
+    index: List[int] = []
+    kinds: List[int] = []
+    metrics: list = []
+    seen = [0, 0]
+
+    def visit(t: MetricsTree, prefix0: Tuple[str, ...], labels0: Labels) -> None:
+        prefix1, labels1 = _rewrite(prefix0, labels0)
+        m = t.metric
+        if isinstance(m, (Metric.Counter, Metric.Gauge)):
+            kind = KIND_COUNTER if isinstance(m, Metric.Counter) else KIND_GAUGE
+            keys.append(escape_key(":".join(prefix1)))
+            inners.append(label_text(labels1))
+            kinds.append(kind)
+            index.append(seen[kind])
+            seen[kind] += 1
+            metrics.append(m)
+        for name, child in t.children.items():
+            visit(child, prefix1 + (name,), labels1)
+
+    visit(tree, (), ())
+    return NameTable.build(keys, inners, index, metrics, kinds)
+
+
+def scalar_values(table: NameTable):
+    """(counters int64, gauges float32) of one scrape: the current values of the counter
+    and gauge rows of a host table, each in the order its rows' ``index`` counts."""
+    from ._native import KIND_COUNTER, KIND_GAUGE
+    counters = [m.get() for m, k in zip(table.metrics, table.kinds) if k == KIND_COUNTER]
+    gauges = [m.get() for m, k in zip(table.metrics, table.kinds) if k == KIND_GAUGE]
+    return np.asarray(counters, np.int64), np.asarray(gauges, np.float32)
+
+
 class PrometheusTelemeter:
     """PrometheusTelemeter (PrometheusTelemeter.scala:17-35): /admin/metrics/prometheus."""
 
@@ -281,7 +327,7 @@ class PrometheusTelemeter:
             write_quantile_metrics(self.metrics, self.quantiles, out)
         return "".join(out)
 
-    def render_bytes(self, engine, names: "NameTable" = None, summaries=None) -> bytes:
+    def render_bytes(self, engine, names: "NameTable" = None, summaries=None, scalars_on_device: bool = False) -> bytes:
         """The exposition as bytes, the Stats' text rendered on the device by ``engine``
         (a HistogramEngine): the counter and gauge lines (printed here: the engine does
         not hold them), the Stat blocks, the rollup blocks if ``rollups`` is set, the
@@ -291,10 +337,18 @@ class PrometheusTelemeter:
         to_device() for the device calls); built here when None.  ``summaries``: the
         snapshot's records indexed by series id, host or device (every Stat of the table
         then prints its record); None takes each Stat's snapshotted summary, and a Stat
-        without one prints nothing."""
-        out: List[str] = []
-        write_scalar_metrics(self.metrics, out)
-        parts = ["".join(out).encode("utf-8")]
+        without one prints nothing.  ``scalars_on_device``: the counter and gauge lines
+        are rendered on the device too (render_json.render_scalars over
+        scalar_name_table(self.metrics)), the same bytes."""
+        if scalars_on_device:
+            from .render_json import render_scalars
+            scalars = scalar_name_table(self.metrics)
+            counters, gauges = scalar_values(scalars)
+            parts = [render_scalars(engine, scalars, counters, gauges) if scalars.n else b""]
+        else:
+            out: List[str] = []
+            write_scalar_metrics(self.metrics, out)
+            parts = ["".join(out).encode("utf-8")]
         table = stat_name_table(self.metrics) if names is None else names
         host = table if table.metrics is not None and isinstance(table.key_off, np.ndarray) else None
         if summaries is not None:
