@@ -498,6 +498,54 @@ int l5dh_render_scalars(l5dh_ctx* ctx, const l5dh_names* names, const uint8_t* k
                         const int64_t* counters, size_t ncounters, const float* gauges, size_t ngauges, uint8_t* out,
                         size_t cap, size_t* len);
 
+/* The InfluxDB line protocol body (/admin/metrics/influxdb) on the device.  A line is a
+ * measurement head followed by the fields of every metric under one parent, sorted
+ * together by key, so the rows of this table are FIELDS in the order they are printed,
+ * beside a small table of lines.  Row j < n belongs to line l = line[j] (non-decreasing,
+ * < nlines) and prints
+ *   ( first row of its line ? head[l] host tail[l] : `,` )  key  `=`  value  ( last row ? `\n` : nothing )
+ * where a row is first when j == 0 or line[j-1] != l, and last when j == n-1 or
+ * line[j+1] != l; a line id without rows prints nothing.  head[l] is
+ * head_bytes[head_off[l] .. head_off[l+1]), the text up to and including `host=`;
+ * host the request's Host value, host_len bytes (0: none); tail[l] the text after it up
+ * to and including the space; key the whole field key, suffix included
+ * (`request_latency_ms_p999`).  The value is the element index[j] of the array of the
+ * row's kind, kinds[j]:
+ *   L5DH_KIND_COUNTER  counters[index[j]]   as l5dh_format_long
+ *   L5DH_KIND_GAUGE    gauges[index[j]]     as l5dh_format_float, never quoted
+ *   L5DH_KIND_STAT     field field[j] (0 .. 10: count, min, max, sum, p50, p90, p95, p99,
+ *                      p9990, p9999, avg -- the L5DH_BY_ numbering) of summaries[index[j]]:
+ *                      a long, or avg as l5dh_format_double; printed whatever the count is
+ * The text is byte for byte what InfluxDbTelemeter writes when the table is built as
+ * linkerd_amd/render_influx.py builds it.
+ *
+ * The contract is that of l5dh_render_json: host or device memory for every data pointer,
+ * host included; *len the exact length; out == NULL a size query; cap < *len -ERANGE with
+ * nothing written; n == 0 writes nothing and sets *len = 0; no engine state read.
+ * -EINVAL before anything is enqueued: a null names or, with n > 0, a null array of it; a
+ * null host with host_len > 0; host_len > 65535; a non-null count with a null value
+ * array; n or nlines above 2^32 - 16.  Found on the device, l5dh_last_error naming the
+ * least such row and the output then unspecified: a kind that is none of the three;
+ * field[j] > 10 on a stat row; index[j] >= the count of the row's kind; line[j] >= nlines
+ * or line[j] < line[j-1]; key_off descending at the row, head_off or tail_off descending at
+ * its line; pieces (head, host, tail and key) above 2^25 bytes (all -EINVAL); an avg
+ * outside l5dh_format_double's domain (-ERANGE). */
+typedef struct {
+  const uint32_t* line;      /* [n] */
+  const uint8_t* kinds;      /* [n] */
+  const uint8_t* field;      /* [n] */
+  const uint32_t* index;     /* [n] */
+  const uint64_t* key_off;   /* [n + 1] */
+  const uint8_t* key_bytes;
+  const uint64_t* head_off;  /* [nlines + 1] */
+  const uint8_t* head_bytes;
+  const uint64_t* tail_off;  /* [nlines + 1] */
+  const uint8_t* tail_bytes;
+} l5dh_influx_names;
+int l5dh_render_influx(l5dh_ctx* ctx, const l5dh_influx_names* names, size_t n, size_t nlines, const uint8_t* host,
+                       size_t host_len, const l5dh_summary* summaries, size_t nsummaries, const int64_t* counters,
+                       size_t ncounters, const float* gauges, size_t ngauges, uint8_t* out, size_t cap, size_t* len);
+
 /* Fleet merge over RCCL (xGMI): sample-sharded series (config C4) summed across
  * contexts on different GPUs.  One communicator per context, one rank per GPU:
  *  - multi-process (or one thread per context): rank 0 calls l5dh_comm_unique_id,

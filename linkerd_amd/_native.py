@@ -63,6 +63,13 @@ class Names(ctypes.Structure):
     _fields_ = [("index", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("key_bytes", ctypes.c_void_p),
                 ("lab_off", ctypes.c_void_p), ("lab_bytes", ctypes.c_void_p)]
 
+
+class InfluxNames(ctypes.Structure):
+    """l5dh_influx_names: the ten arrays of an InfluxDB table (render_influx.InfluxTable)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("line", "kinds", "field", "index", "key_off", "key_bytes", "head_off",
+                                               "head_bytes", "tail_off", "tail_bytes")]
+
+
 MERGE_REDUCE_SCATTER = 0
 MERGE_ALL_REDUCE = 1
 UNIQUE_ID_BYTES = 128
@@ -129,6 +136,8 @@ SIGNATURES = {
                                     _vp, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "l5dh_render_scalars": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp,
                                        _c.c_size_t, _c.POINTER(_c.c_size_t)]),
+    "l5dh_render_influx": (_c.c_int, [_vp, _vp, _c.c_size_t, _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t, _vp,
+                                      _c.c_size_t, _vp, _c.c_size_t, _vp, _c.c_size_t, _c.POINTER(_c.c_size_t)]),
     "l5dh_sync": (_c.c_int, [_vp]),
     "l5dh_set_stream": (_c.c_int, [_vp, _vp]),
     "l5dh_wait_event": (_c.c_int, [_vp, _vp]),

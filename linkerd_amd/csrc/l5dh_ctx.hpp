@@ -15,6 +15,7 @@
 
 #include "../../include/l5dhist.h"
 #include "l5dh_import.hpp"
+#include "l5dh_influx.hpp"
 #include "l5dh_kernels.hpp"
 #include "l5dh_le.hpp"
 #include "l5dh_merge.hpp"
@@ -158,6 +159,8 @@ struct l5dh_ctx {
   DevBuf rd_index, rd_koff, rd_kbytes, rd_loff, rd_lbytes, rd_vals, rd_sums, rd_le, rd_out;
   DevBuf rd_len, rd_offs, rd_avg, rd_flags, rd_tmp;
   DevBuf rd_kinds, rd_counters, rd_gauges;  // the JSON and scalar blocks' staged kinds and values
+  // the InfluxDB renderer (l5dh_influx.hip): what its table has beyond the arrays staged above, and its flag words
+  DevBuf ifx_line, ifx_field, ifx_hoff, ifx_hbytes, ifx_toff, ifx_tbytes, ifx_host, ifx_flags;
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params

@@ -553,6 +553,92 @@ int rd_kind_check(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kinds, si
   return 0;
 }
 
+// ---- the InfluxDB renderer -----------------------------------------------------------
+// The findings of its passes, in the order the header lists them.
+int ifx_findings(l5dh_ctx* c, const uint32_t* f) {
+  const uint32_t none = 0xFFFFFFFFu;
+  auto row = [&](int w) { return std::to_string(f[w]); };
+  if (f[IF_KIND] != none) return fail(c, -EINVAL, "render_influx: the kind of row " + row(IF_KIND) + " is none of the three");
+  if (f[IF_FIELD] != none) return fail(c, -EINVAL, "render_influx: field of row " + row(IF_FIELD) + " is above 10");
+  if (f[IF_BADIDX] != none)
+    return fail(c, -EINVAL, "render_influx: index of row " + row(IF_BADIDX) + " is not < the count of its kind");
+  if (f[IF_LINE] != none)
+    return fail(c, -EINVAL, "render_influx: line of row " + row(IF_LINE) + " is not < nlines, or descends");
+  if (f[IF_KEYOFF] != none) return fail(c, -EINVAL, "render_influx: key_off descends at row " + row(IF_KEYOFF));
+  if (f[IF_LINEOFF] != none)
+    return fail(c, -EINVAL, "render_influx: head_off or tail_off descends at the line of row " + row(IF_LINEOFF));
+  if (f[IF_LONG] != none)
+    return fail(c, -EINVAL, "render_influx: head, host, tail and key of row " + row(IF_LONG) + " exceed 2^25 bytes");
+  if (f[IF_RANGE] != none)
+    return fail(c, -ERANGE,
+                "render_influx: avg of row " + row(IF_RANGE) + " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
+  if (f[IF_MISMATCH] != none)
+    return fail(c, -EIO, "internal: the render_influx passes disagree on the length of row " + row(IF_MISMATCH));
+  return 0;
+}
+
+// The passes over n > 0 rows.  The caller holds the lock and has checked the arguments; r
+// holds the caller's pointers, staged here where they are not used in place.
+int do_render_influx(l5dh_ctx* c, InfluxRows r, size_t n, uint8_t* out, size_t cap, size_t* len) {
+  int rc;
+  const size_t nl = r.nlines;
+  const uint64_t *koff = r.key_off, *hoff = r.head_off, *toff = r.tail_off;  // (the caller's: rd_stage_bytes reads their ends)
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((rc = rd_stage_bytes(c, r.key_bytes, koff, n, c->rd_kbytes)) ||
+        (rc = rd_stage_bytes(c, r.head_bytes, hoff, nl, c->ifx_hbytes)) ||
+        (rc = rd_stage_bytes(c, r.tail_bytes, toff, nl, c->ifx_tbytes)) ||
+        (rc = stage_in(c, r.line, n, 4, c->ifx_line)) || (rc = stage_in(c, r.kinds, n, 1, c->rd_kinds)) ||
+        (rc = stage_in(c, r.field, n, 1, c->ifx_field)) || (rc = stage_in(c, r.index, n, 4, c->rd_index)) ||
+        (rc = stage_in(c, r.key_off, n + 1, 8, c->rd_koff)) || (rc = stage_in(c, r.head_off, nl + 1, 8, c->ifx_hoff)) ||
+        (rc = stage_in(c, r.tail_off, nl + 1, 8, c->ifx_toff)) ||
+        (rc = stage_in(c, r.host, (size_t)r.host_len, 1, c->ifx_host)) ||
+        (rc = stage_in(c, r.summaries, (size_t)r.nsummaries, 8, c->rd_vals)) ||
+        (rc = stage_in(c, r.counters, (size_t)r.ncounters, 8, c->rd_counters)) ||
+        (rc = stage_in(c, r.gauges, (size_t)r.ngauges, 4, c->rd_gauges)))
+      return rc;
+  }
+  size_t tmp_bytes = 0;
+  HIPCHK(c, merge_count(nullptr, (uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  if ((rc = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT)) || (rc = ensure(c, c->rd_len, (n + 1) * 4)) ||
+      (rc = ensure(c, c->rd_offs, (n + 1) * 8)) || (rc = ensure(c, c->ifx_flags, IF_WORDS * 4)) ||
+      (rc = ensure(c, c->rd_tmp, tmp_bytes)))
+    return rc;
+  r.slot = c->rd_avg.as<uint8_t>();
+  uint32_t* flags = c->ifx_flags.as<uint32_t>();
+  uint64_t* offs = c->rd_offs.as<uint64_t>();
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, hipMemsetAsync(flags, 0xFF, IF_WORDS * 4, c->stream));
+    HIPCHK(c, influx_lengths(r, (uint32_t)n, c->rd_len.as<uint32_t>(), flags, c->stream));
+    HIPCHK(c, merge_count(nullptr, (uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
+  }
+  // the device's findings and the text's length: one host wait, before anything is written
+  uint32_t hf[IF_WORDS];
+  uint64_t total = 0;
+  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = sync_stream(c)) || (rc = ifx_findings(c, hf))) return rc;
+  if (len) *len = (size_t)total;
+  if (!out) return 0;  // a size query
+  if (cap < total)
+    return fail(c, -ERANGE,
+                "render_influx: the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
+  StagedOut<uint8_t> o;
+  if ((rc = o.begin(c, out, (size_t)total, c->rd_out, 1))) return rc;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    if (total) HIPCHK(c, influx_write(r, (uint32_t)n, offs, o.dev, flags, c->stream));
+  }
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((rc = o.end(c))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((rc = sync_stream(c))) return rc;
+  return ifx_findings(c, hf);
+}
+
 }  // namespace
 
 extern "C" {
@@ -815,6 +901,48 @@ int l5dh_render_scalars(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kin
   int r = rd_kind_check(c, names, kinds, n, true, k, 0, ncounters, ngauges, len);
   if (r) return r < 0 ? r : 0;
   return do_render(c, names, n, 0, ScalarRows{k}, out, cap, len);
+}
+
+int l5dh_render_influx(l5dh_ctx* c, const l5dh_influx_names* names, size_t n, size_t nlines, const uint8_t* host,
+                       size_t host_len, const l5dh_summary* summaries, size_t nsummaries, const int64_t* counters,
+                       size_t ncounters, const float* gauges, size_t ngauges, uint8_t* out, size_t cap, size_t* len) {
+  if (!c) return -EINVAL;
+  CtxLock g(c);
+  if (len) *len = 0;
+  if (!names) return fail(c, -EINVAL, "render_influx: null names");
+  if (n && (!names->line || !names->kinds || !names->field || !names->index || !names->key_off || !names->key_bytes ||
+            !names->head_off || !names->head_bytes || !names->tail_off || !names->tail_bytes))
+    return fail(c, -EINVAL, "render_influx: a null array of names");
+  if (host_len && !host) return fail(c, -EINVAL, "render_influx: null host with a length above 0");
+  if (host_len > 65535) return fail(c, -EINVAL, "render_influx: host_len above 65535");
+  if ((nsummaries && !summaries) || (ncounters && !counters) || (ngauges && !gauges))
+    return fail(c, -EINVAL, "render_influx: a null value array with a count above 0");
+  if (n > 0xFFFFFFF0ull || nlines > 0xFFFFFFF0ull || nsummaries > 0xFFFFFFFFull || ncounters > 0xFFFFFFFFull ||
+      ngauges > 0xFFFFFFFFull)
+    return fail(c, -EINVAL, "render_influx: more than 2^32 - 16 rows or lines");
+  if (n == 0) return 0;
+  static_assert(sizeof(l5dh_summary) == sizeof(Summary88), "l5dh_summary layout");
+  InfluxRows r{};
+  r.line = names->line;
+  r.kinds = names->kinds;
+  r.field = names->field;
+  r.index = names->index;
+  r.key_off = names->key_off;
+  r.key_bytes = names->key_bytes;
+  r.head_off = names->head_off;
+  r.head_bytes = names->head_bytes;
+  r.tail_off = names->tail_off;
+  r.tail_bytes = names->tail_bytes;
+  r.host = host;
+  r.host_len = (uint32_t)host_len;
+  r.nlines = (uint32_t)nlines;
+  r.summaries = reinterpret_cast<const Summary88*>(summaries);
+  r.counters = counters;
+  r.gauges = gauges;
+  r.nsummaries = (uint32_t)nsummaries;
+  r.ncounters = (uint32_t)ncounters;
+  r.ngauges = (uint32_t)ngauges;
+  return do_render_influx(c, r, n, out, cap, len);
 }
 
 }  // extern "C"

@@ -102,3 +102,25 @@ class InfluxDbTelemeter:
         out: List[str] = []
         write_metrics(self.metrics, out, (), (("host", host),))
         return "".join(out)
+
+    def render_bytes(self, engine, host: str = "none", table=None, summaries=None) -> bytes:
+        """render(host) as UTF-8 bytes, rendered on the device by ``engine`` (a
+        HistogramEngine) -- the same bytes.  ``table``: render_influx.influx_table(self.metrics)
+        kept by the caller (a host table); built here when None.  ``summaries``: the
+        snapshot's records indexed by series id, host or device -- every Stat with a series
+        id then prints its record; None takes each Stat's snapshotted summary, and a Stat
+        without one prints nothing.  A body with an avg outside the device formatter's
+        domain is the host writer's text."""
+        import errno
+
+        from ._native import L5dhError
+        from .render_influx import influx_table, render_influx, scrape_inputs
+        if table is None:
+            table = influx_table(self.metrics)
+        table, records, counters, gauges = scrape_inputs(table, summaries)
+        try:
+            return render_influx(engine, table, host, records, counters, gauges)
+        except L5dhError as e:
+            if e.code != -errno.ERANGE:
+                raise
+            return self.render(host).encode("utf-8")

@@ -1,0 +1,284 @@
+"""The InfluxDB line protocol body rendered on the device (l5dh_render_influx): the table
+of a tree, its pure-Python replay, and the call over a HistogramEngine's argument rules.
+
+An InfluxDB line is a measurement head followed by the fields of every metric directly
+under one parent, sorted together by key, so the rows of the table are **fields** in the
+order they are printed, beside a small table of **lines**.  Row j prints
+
+    ( first row of its line ? head[l] host tail[l] : "," )  key  "="  value  ( last row of its line ? "\\n" : "" )
+
+with l = line[j]; a row is first when j == 0 or line[j-1] != l, last when j == n-1 or
+line[j+1] != l.  A line id without rows prints nothing, so take() drops the eleven rows of
+a Stat without a snapshot and renumbers nothing.  render_host is that grammar in Python:
+the table's executable specification.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _native as N
+from .engine import QUERY, _numel, _record_rows  # noqa: F401  (QUERY: for the callers)
+from .influxdb import ROOT_PREFIX, _rewrite, _utf16_key, escape_key
+from .javafmt import double_to_string, float_to_string, long_to_string
+from .prometheus import NO_INDEX
+from .telemetry import Metric, MetricsTree
+
+# a Stat's fields in influxdb._fields' order: (key suffix, the field's index in the summary record)
+STAT_FIELDS = (("_count", N.BY_COUNT), ("_sum", N.BY_SUM), ("_avg", N.BY_AVG), ("_min", N.BY_MIN), ("_max", N.BY_MAX),
+               ("_p50", N.BY_P50), ("_p90", N.BY_P90), ("_p95", N.BY_P95), ("_p99", N.BY_P99), ("_p999", N.BY_P9990),
+               ("_p9999", N.BY_P9999))
+
+
+def _pack(texts):
+    enc = [t.encode("utf-8") for t in texts]
+    off = np.zeros(len(enc) + 1, np.uint64)
+    off[1:] = np.cumsum(np.asarray([len(b) for b in enc], np.uint64))
+    return off, np.frombuffer(b"".join(enc), np.uint8).copy()
+
+
+class InfluxTable:
+    """What l5dh_render_influx needs of the names, none of which varies per scrape.  Per
+    field row: ``line`` (uint32, non-decreasing, < nlines), ``kinds`` (uint8, _native.KIND_*),
+    ``field`` (uint8: a stat row's field in the summary record, the BY_* numbering),
+    ``index`` (uint32: the element of the row's kind's value array) and the whole field key
+    as UTF-8 behind ``key_off`` / ``key_bytes``.  Per line: the text up to and including
+    ``host=`` (``head_off`` / ``head_bytes``) and the text after the host value up to and
+    including the space (``tail_off`` / ``tail_bytes``).  Host tables also keep ``metrics``,
+    the metric behind each row, ``stats``, the tree's Stats, and ``stat_ord``, a stat row's
+    Stat in that list."""
+
+    def __init__(self, line, kinds, field, index, key_off, key_bytes, head_off, head_bytes, tail_off, tail_bytes,
+                 metrics=None, stats=None, stat_ord=None):
+        self.line, self.kinds, self.field, self.index = line, kinds, field, index
+        self.key_off, self.key_bytes = key_off, key_bytes
+        self.head_off, self.head_bytes, self.tail_off, self.tail_bytes = head_off, head_bytes, tail_off, tail_bytes
+        self.metrics, self.stats, self.stat_ord = metrics, stats, stat_ord
+
+    @property
+    def n(self) -> int:
+        return int(self.key_off.shape[0]) - 1
+
+    @property
+    def nlines(self) -> int:
+        return int(self.head_off.shape[0]) - 1
+
+    def with_index(self, index) -> "InfluxTable":
+        """The same rows printing other elements of the value arrays."""
+        t = InfluxTable(*self._arrays())
+        t.index = index
+        return t
+
+    def _arrays(self):
+        return (self.line, self.kinds, self.field, self.index, self.key_off, self.key_bytes, self.head_off,
+                self.head_bytes, self.tail_off, self.tail_bytes, self.metrics, self.stats, self.stat_ord)
+
+    def take(self, rows) -> "InfluxTable":
+        """The table of the given field rows, in that order (a host table); the lines stay
+        as they are."""
+        rows = np.asarray(rows, np.int64)
+        start = self.key_off[rows].astype(np.int64)
+        length = self.key_off[rows + 1].astype(np.int64) - start
+        key_off = np.zeros(rows.size + 1, np.uint64)
+        key_off[1:] = np.cumsum(length.astype(np.uint64))
+        src = np.repeat(start - key_off[:-1].astype(np.int64), length) + np.arange(int(key_off[-1]), dtype=np.int64)
+        metrics = None if self.metrics is None else [self.metrics[int(r)] for r in rows]
+        stat_ord = None if self.stat_ord is None else self.stat_ord[rows]
+        return InfluxTable(self.line[rows], self.kinds[rows], self.field[rows], self.index[rows], key_off,
+                           self.key_bytes[src], self.head_off, self.head_bytes, self.tail_off, self.tail_bytes, metrics,
+                           self.stats, stat_ord)
+
+    def to_device(self, device: int = 0) -> "InfluxTable":
+        """The same table in device memory (torch tensors): uploaded once, reused by every
+        scrape."""
+        import torch
+        dev = torch.device("cuda", int(device))
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            # (the same bits under torch's long-standing signed types)
+            a = a.view({8: np.int64, 4: np.int32}.get(a.dtype.itemsize, np.uint8)) if a.dtype.kind == "u" else a
+            return torch.from_numpy(a).to(dev)
+        return InfluxTable(*[up(a) for a in self._arrays()[:10]], self.metrics, self.stats, self.stat_ord)
+
+
+def influx_table(tree: MetricsTree) -> InfluxTable:
+    """The table of ``tree``, walked exactly as influxdb.write_metrics walks it under the
+    tags ``host=<host>``: lines numbered as they are emitted (post-order, deeper lines
+    first), the same prefix rewrite, escape and ``root`` prefix, the same stable sorts by
+    UTF-16 code units over a line's fields in child order and over its tags.  Every Stat has
+    its eleven rows, snapshot or not; a stat row's ``index`` is the series id (NO_INDEX
+    without one), a counter's or gauge's its ordinal among the table's rows of its kind."""
+    line: List[int] = []
+    kinds: List[int] = []
+    field: List[int] = []
+    keys: List[str] = []
+    metrics: list = []
+    stat_ord: List[int] = []
+    stats: list = []
+    heads: List[str] = []
+    tails: List[str] = []
+    HOST = ("host", "")  # the request's tag: found again by identity after the sort
+    suffixes = [sfx for sfx, _ in STAT_FIELDS]
+    stat_kinds, stat_words = [N.KIND_STAT] * 11, [f for _, f in STAT_FIELDS]
+
+    def visit(t: MetricsTree, prefix0: Tuple[str, ...], tags0) -> None:
+        prefix1, tags1 = _rewrite(prefix0, tags0)
+        # the line's fields in child order, a column each (no object per field: a tree of 10^5 Stats has 10^6)
+        ks, kd, fl, ms, so = [], [], [], [], []
+        for name, child in t.children.items():
+            visit(child, prefix1 + (name,), tags1)  # deeper lines first
+            m = child.metric
+            if isinstance(m, Metric.Stat):
+                ks += [name + sfx for sfx in suffixes]
+                kd += stat_kinds
+                fl += stat_words
+                ms += [m] * 11
+                so += [len(stats)] * 11
+                stats.append(m)
+            elif isinstance(m, (Metric.Counter, Metric.Gauge)):
+                ks.append(name)
+                kd.append(N.KIND_COUNTER if isinstance(m, Metric.Counter) else N.KIND_GAUGE)
+                fl.append(0)
+                ms.append(m)
+                so.append(0)
+        if not ks:
+            return
+        # the tags split at the host entry itself (tag values are arbitrary text: no placeholder is searched for)
+        tags = sorted(tags1, key=_utf16_key)
+        at = next(i for i, kv in enumerate(tags) if kv is HOST)
+        measurement = escape_key(":".join(prefix1 if prefix1 else ROOT_PREFIX))
+        heads.append(measurement + "".join(f",{k}={v}" for k, v in tags[:at]) + ",host=")
+        tails.append("".join(f",{k}={v}" for k, v in tags[at + 1:]) + " ")
+        # the stable sort by key, as a permutation (ASCII keys: the code-point order is the UTF-16 order)
+        ascii_keys = all(map(str.isascii, ks))
+        order = sorted(range(len(ks)), key=ks.__getitem__ if ascii_keys else lambda i: _utf16_key((ks[i],)))
+        line.extend([len(heads) - 1] * len(ks))
+        for column, values in ((keys, ks), (kinds, kd), (field, fl), (metrics, ms), (stat_ord, so)):
+            column.extend([values[i] for i in order])
+
+    visit(tree, (), (HOST,))
+    kinds_a = np.asarray(kinds, np.uint8)
+    # a stat row's index is its Stat's series id; a counter's or a gauge's its ordinal among the rows of its kind
+    ids = np.asarray([NO_INDEX if m.series_id is None else int(m.series_id) for m in stats] + [NO_INDEX], np.int64)
+    index = ids[np.asarray(stat_ord, np.int64)] if kinds else np.zeros(0, np.int64)
+    for kind in (N.KIND_COUNTER, N.KIND_GAUGE):
+        rows = kinds_a == kind
+        index[rows] = np.arange(int(rows.sum()))
+    key_off, key_bytes = _pack(keys)
+    head_off, head_bytes = _pack(heads)
+    tail_off, tail_bytes = _pack(tails)
+    return InfluxTable(np.asarray(line, np.uint32), kinds_a, np.asarray(field, np.uint8), index.astype(np.uint32), key_off,
+                       key_bytes, head_off, head_bytes, tail_off, tail_bytes, metrics, stats,
+                       np.asarray(stat_ord, np.uint32))
+
+
+def influx_values(table: InfluxTable):
+    """(counters int64, gauges float32) of one scrape: the current values of the counter and
+    gauge rows of a host table, each at the element its row's ``index`` names."""
+    out = []
+    for kind, dtype in ((N.KIND_COUNTER, np.int64), (N.KIND_GAUGE, np.float32)):
+        rows = np.flatnonzero(table.kinds == kind)
+        values = np.zeros(int(table.index[rows].max()) + 1 if rows.size else 0, dtype)
+        values[table.index[rows]] = [table.metrics[int(j)].get() for j in rows]
+        out.append(values)
+    return tuple(out)
+
+
+def scrape_inputs(table: InfluxTable, summaries=None):
+    """(table, summaries, counters, gauges) of one scrape of a host table, as render_influx
+    takes them.  ``summaries``: the snapshot's records indexed by series id, host or device
+    -- the rows of a Stat without a series id are dropped; None takes each Stat's
+    snapshotted summary, its index its ordinal among the Stats that have one, and drops
+    the rows of a Stat without one.  An empty value array is None."""
+    from .prometheus import summary_records
+    stat = table.kinds == N.KIND_STAT
+    counters, gauges = influx_values(table)
+    if summaries is not None:
+        keep = ~stat | (table.index != NO_INDEX)
+    else:
+        snaps = [m.snapshotted_summary for m in table.stats]
+        has = np.asarray([s is not None for s in snaps], bool)
+        shown = [s for s in snaps if s is not None]
+        summaries = summary_records(shown) if shown else None
+        keep = ~stat
+        if has.size:
+            keep = keep | has[table.stat_ord]
+            ordinal = (np.cumsum(has) - 1).astype(np.uint32)
+            table = table.with_index(np.where(stat, ordinal[table.stat_ord], table.index).astype(np.uint32))
+    if not keep.all():
+        table = table.take(np.flatnonzero(keep))
+    return table, summaries, counters if counters.size else None, gauges if gauges.size else None
+
+
+def _host_bytes(host) -> bytes:
+    return host.encode("utf-8") if isinstance(host, str) else bytes(host)
+
+
+def render_host(table: InfluxTable, host, summaries, counters, gauges) -> bytes:
+    """The row grammar replayed in Python over the arrays of a host table, numbers by
+    javafmt: what l5dh_render_influx writes.  ``summaries``: the numpy summary dtype."""
+    host = _host_bytes(host)
+    n, line = table.n, table.line
+    key, head, tail = table.key_bytes.tobytes(), table.head_bytes.tobytes(), table.tail_bytes.tobytes()
+    ko, ho, to = ([int(x) for x in off] for off in (table.key_off, table.head_off, table.tail_off))
+    out: List[bytes] = []
+    for j in range(n):
+        l, kind, i = int(line[j]), int(table.kinds[j]), int(table.index[j])
+        if j == 0 or int(line[j - 1]) != l:
+            out += [head[ho[l]:ho[l + 1]], host, tail[to[l]:to[l + 1]]]
+        else:
+            out.append(b",")
+        out += [key[ko[j]:ko[j + 1]], b"="]
+        if kind == N.KIND_COUNTER:
+            text = long_to_string(int(counters[i]))
+        elif kind == N.KIND_GAUGE:
+            text = float_to_string(float(gauges[i]))
+        else:
+            f = int(table.field[j])
+            v = summaries[i][N.SUMMARY_FIELDS[f]]
+            text = double_to_string(float(v)) if f == N.BY_AVG else long_to_string(int(v))
+        out.append(text.encode("ascii"))
+        if j == n - 1 or int(line[j + 1]) != l:
+            out.append(b"\n")
+    return b"".join(out)
+
+
+def influx_names(engine, table: InfluxTable) -> "N.InfluxNames":
+    """The l5dh_influx_names of a table (numpy arrays, or torch tensors on the engine's
+    GPU): every array checked as every other buffer is."""
+    n, nl = table.n, table.nlines
+    return N.InfluxNames(engine._buf(table.line, (np.uint32, np.int32), "table.line", n),
+                         engine._buf(table.kinds, (np.uint8,), "table.kinds", n),
+                         engine._buf(table.field, (np.uint8,), "table.field", n),
+                         engine._buf(table.index, (np.uint32, np.int32), "table.index", n),
+                         engine._buf(table.key_off, (np.uint64, np.int64), "table.key_off", n + 1),
+                         engine._buf(table.key_bytes, (np.uint8,), "table.key_bytes"),
+                         engine._buf(table.head_off, (np.uint64, np.int64), "table.head_off", nl + 1),
+                         engine._buf(table.head_bytes, (np.uint8,), "table.head_bytes"),
+                         engine._buf(table.tail_off, (np.uint64, np.int64), "table.tail_off", nl + 1),
+                         engine._buf(table.tail_bytes, (np.uint8,), "table.tail_bytes"))
+
+
+def render_influx(engine, table: InfluxTable, host, summaries, counters, gauges, out=None):
+    """The body of /admin/metrics/influxdb of the rows of ``table`` under the request's
+    ``host`` (str, UTF-8 encoded, or bytes), byte for byte InfluxDbTelemeter.render's text:
+    a counter row prints counters[index] (int64) as a Java long, a gauge row gauges[index]
+    (float32) as Float.toString (never quoted), a stat row field ``field`` of
+    summaries[index] (the numpy summary dtype or int64 [n*11]) -- whatever its count is.
+    Each value array is host or device memory, or None when no row is of its kind.  Answers
+    as render_json does: bytes, or with ``out`` the length written there, or with out=QUERY
+    the length alone.  Reads no engine state."""
+    from .render_json import _values
+    sp, ns = None, 0
+    if summaries is not None:
+        sp, ns = engine._records(summaries, N.SUMMARY_DTYPE, "summaries"), _record_rows(summaries, N.SUMMARY_DTYPE)[0]
+    cp, nc = _values(engine, counters, (np.int64,), "counters")
+    gp, ng = _values(engine, gauges, (np.float32,), "gauges")
+    hb = np.frombuffer(_host_bytes(host), np.uint8)
+    nm, n, nl = influx_names(engine, table), table.n, table.nlines
+    return engine._render(lambda op, cap, ln: engine._lib.l5dh_render_influx(
+        engine._ctx, ctypes.byref(nm), n, nl, hb.ctypes.data if hb.size else None, _numel(hb), sp, ns, cp, nc, gp, ng,
+        op, cap, ln), "l5dh_render_influx", out)
