@@ -2,9 +2,13 @@
 // test infrastructure; not part of the engine).  Same counter-based recipe as
 // linkerd_amd/synth.py: rand(seed, stream, i) = mix64(((seed<<48) ^ (stream<<40)
 // ^ i) + 1) * GOLD), Box-Muller normals, float32(exp(mu + sigma*z)) clamped to
-// [0, 1e9].  Device libm may differ from numpy in the last ulp, so values are
-// recipe-equivalent, not bit-identical to synth.py; parity tests always feed
-// the same bytes to the engine and to the oracle.
+// [0, 1e9].  Device libm may differ from numpy in the last ulp of a double, so
+// values are recipe-equivalent, not promised bit-identical to synth.py; parity
+// tests always feed the same bytes to the engine and to the oracle.  Pinned by
+// tests/test_gpu_synth.py: series ids equal to synth.py's on the same arguments
+// (base_index, series_base, a restricted CDF, bench.gen_batch's own calls, the
+// grid-stride tail), every value within one float32 ulp and at most 1 in 10^4
+// different at all; synth.py itself is pinned to the recipe by tests/test_synth_host.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -11,6 +11,9 @@ Recipe:
   C2: S series x K samples; mu_s = ln U[1,1000] (stream 1, index s), sigma 0.8;
       COO position i holds sample j = (i*A + B) mod N of series j // K.
   C3: series = Zipf(s=1) rank (inverse CDF over 1/r), values as C2.
+  A shard of C2 / C3 (bench.py) keeps local series ids; series_base, the shard's first
+  global id, only shifts the index that seeds mu (u32 arithmetic, as in the kernels),
+  and C3 draws its ranks from the CDF it is given (default: zipf_cdf(S)).
 """
 from __future__ import annotations
 
@@ -70,12 +73,17 @@ def c1(n: int = 10_000_000, seed: int = 1):
     return np.zeros(n, dtype=np.uint32), vals
 
 
-def c2(S: int = 100_000, K: int = 1_000, seed: int = 2, sigma: float = 0.8):
+def _global_ids(series: np.ndarray, series_base: int) -> np.ndarray:
+    with np.errstate(over="ignore"):
+        return series + np.uint32(series_base)
+
+
+def c2(S: int = 100_000, K: int = 1_000, seed: int = 2, sigma: float = 0.8, series_base: int = 0):
     N = S * K
     i = np.arange(N, dtype=np.uint64)
     j = (i * np.uint64(PERM_A) + np.uint64(PERM_B)) % np.uint64(N)
     series = (j // np.uint64(K)).astype(np.uint32)
-    mu = series_mu(seed, series)
+    mu = series_mu(seed, _global_ids(series, series_base))
     vals = lognormal_f32(mu, sigma, normal(seed, 2, j))
     return series, vals
 
@@ -86,11 +94,13 @@ def zipf_cdf(S: int, s: float = 1.0) -> np.ndarray:
     return c / c[-1]
 
 
-def c3(S: int = 1_000_000, N: int = 1_000_000_000, seed: int = 3, sigma: float = 0.8, base_index: int = 0):
+def c3(S: int = 1_000_000, N: int = 1_000_000_000, seed: int = 3, sigma: float = 0.8, base_index: int = 0,
+       cdf=None, series_base: int = 0):
     idx = np.arange(base_index, base_index + N, dtype=np.uint64)
     u = uniform(seed, 3, idx)
-    cdf = zipf_cdf(S)
+    if cdf is None:
+        cdf = zipf_cdf(S)
     series = np.minimum(np.searchsorted(cdf, u, side="right"), S - 1).astype(np.uint32)
-    mu = series_mu(seed, series)
+    mu = series_mu(seed, _global_ids(series, series_base))
     vals = lognormal_f32(mu, sigma, normal(seed, 2, idx))
     return series, vals
