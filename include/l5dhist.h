@@ -102,7 +102,8 @@ enum {
   L5DH_K_COPY = 5,   /* H2D/D2H staging copies */
   L5DH_K_BIN2 = 6,   /* level-2 partition (super-tile regions -> 16-bit per-key records, + its redo) */
   L5DH_K_MERGE = 7,  /* the RCCL collective of l5dh_merge */
-  L5DH_K_NKERNELS = 8
+  L5DH_K_WINDOW = 8, /* the sliding window's sum over its slots (l5dh_window_query) */
+  L5DH_K_NKERNELS = 9
 };
 
 /* Reference: BucketedHistogram() per Stat (MetricsTree.scala:88).  Opens a
@@ -389,6 +390,62 @@ int l5dh_export_sparse(l5dh_ctx* ctx, uint32_t first, uint32_t count, uint64_t* 
  * or >= max_series.  first + n > max_series (series == NULL) is -EINVAL, found on the host. */
 int l5dh_import_sparse(l5dh_ctx* ctx, const uint32_t* series, uint32_t first, size_t n, const uint64_t* row_off,
                        const l5dh_bucket_entry* entries, const int64_t* totals);
+
+/* Sliding windows: exact summaries over the last W ended intervals ("p99 over the last five
+ * minutes").  A window is a ring of at most L5DH_WINDOW_MAX slots that belongs to a context;
+ * a slot holds, in device memory, the sparse rows (the CSR of l5dh_export_sparse) and exact
+ * totals of one ended interval.  The histogram of a union of intervals is the element-wise
+ * integer sum of their bucket rows, so a series' window summary is byte for byte what ONE
+ * Stat would report had it received every sample the series received in those intervals.
+ * Every data pointer may be host or device memory; every call holds the context's lock.
+ *
+ * l5dh_window_open: slots in [1, L5DH_WINDOW_MAX], else -EINVAL; -EEXIST if the context
+ * already has a window.  l5dh_window_close frees the ring (-EINVAL without one); l5dh_close
+ * frees it too.
+ *
+ * l5dh_window_push ends the interval of series [0, count): l5dh_export_sparse(0, count, ...,
+ * reset = 1) with the ring's next slot as destination, under one hold of the lock, and
+ * series_out (nullable: count l5dh_summary) the interval's summaries from the same state, as
+ * l5dh_snapshot(0, count, ..., reset = 1) would report them.  The oldest slot is overwritten
+ * once the ring is full.  A slot remembers its count: a series at or beyond it has an empty
+ * row in that slot.  Pushes are numbered from 1.  When an allocation fails the call returns
+ * -ENOMEM, resets nothing and leaves the ring as it was.
+ *
+ * l5dh_window_query sums, per series of [first, first + count), the rows of the `last` most
+ * recent slots and, with include_open != 0, the open interval's live row (staged samples are
+ * binned and pending segments folded first, as in l5dh_le; the open interval is not changed).
+ * Per series the outputs (each nullable) receive: out the summary, counts_out [count][1798]
+ * the summed dense row, totals_out the summed exact sum (an int64 that wraps like a Java
+ * long) -- what every other row source returns, so they feed l5dh_top_summaries,
+ * l5dh_render_summaries, l5dh_quantiles_dense, l5dh_le_dense and l5dh_rollup_dense
+ * unchanged.  last == 0 with include_open equals l5dh_snapshot(first, count, ..., reset = 0)
+ * byte for byte.  -EINVAL, found on the host before anything is enqueued: no window, a range
+ * out of bounds, last above the number of filled slots, last == 0 without include_open.  A
+ * bucket sum above 2^31 - 1 is -ERANGE, found on the device and never wrapped (also when
+ * the sum passes 2^32), l5dh_last_error naming the least such series; ring and state are
+ * untouched and the outputs unspecified.
+ *
+ * l5dh_window_forget makes series [first, first + count) start their history now: a query
+ * ignores, for those series, every slot pushed so far (a pruned id's past stays out of the
+ * next Stat that gets the id).  The open interval is not touched.
+ *
+ * l5dh_window_move hands the whole ring of `from` to `to`, a context on the same device
+ * that has none (-EEXIST) and holds at least as many series as the largest slot count
+ * (-EINVAL): pointers move, nothing is copied but the per-series forget marks, extended with
+ * zeros to `to`'s series count.  The two locks are taken in address order.
+ *
+ * l5dh_window_info (every pointer nullable): the ring's slots, the filled ones, the pushes so
+ * far, the entries (8 B each) the filled slots hold, and the device bytes the ring owns. */
+#define L5DH_WINDOW_MAX 64
+int l5dh_window_open(l5dh_ctx* ctx, uint32_t slots);
+int l5dh_window_close(l5dh_ctx* ctx);
+int l5dh_window_push(l5dh_ctx* ctx, uint32_t count, l5dh_summary* series_out /* [count], nullable */);
+int l5dh_window_query(l5dh_ctx* ctx, uint32_t first, uint32_t count, uint32_t last, int include_open,
+                      l5dh_summary* out, int32_t* counts_out, int64_t* totals_out);
+int l5dh_window_forget(l5dh_ctx* ctx, uint32_t first, uint32_t count);
+int l5dh_window_move(l5dh_ctx* from, l5dh_ctx* to);
+int l5dh_window_info(l5dh_ctx* ctx, uint32_t* slots, uint32_t* filled, uint64_t* pushes, uint64_t* entries,
+                     uint64_t* bytes);
 
 /* Java number texts, as the exporters print them (host only, no context): Long.toString,
  * the unsigned 64-bit decimal (the `le` counts) and Double.toString as JDK 8 prints it

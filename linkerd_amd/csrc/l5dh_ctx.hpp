@@ -1,5 +1,5 @@
 // l5dh_ctx.hpp -- private to the host side (l5dh_engine.cpp, l5dh_queries.cpp,
-// l5dh_fleet.cpp): the context behind the C-ABI's opaque l5dh_ctx, the owner of its
+// l5dh_fleet.cpp, l5dh_window_host.cpp): the context behind the C-ABI's opaque l5dh_ctx, the owner of its
 // device memory, and the helpers the files share (defined in l5dh_engine.cpp).
 #pragma once
 
@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -23,6 +24,7 @@
 #include "l5dh_render.hpp"
 #include "l5dh_rollup.hpp"
 #include "l5dh_top.hpp"
+#include "l5dh_window.hpp"
 
 namespace l5dh {
 
@@ -161,6 +163,23 @@ struct l5dh_ctx {
   DevBuf rd_kinds, rd_counters, rd_gauges;  // the JSON and scalar blocks' staged kinds and values
   // the InfluxDB renderer (l5dh_influx.hip): what its table has beyond the arrays staged above, and its flag words
   DevBuf ifx_line, ifx_field, ifx_hoff, ifx_hbytes, ifx_toff, ifx_tbytes, ifx_host, ifx_flags;
+  // the sliding window (l5dh_window_host.cpp): a ring of ended intervals, each slot the CSR of
+  // one sparse export (row_off [count + 1], 8-byte entries, totals [count]) with the series
+  // it covers and its push number; born [born_n] u64: the push number at which a series'
+  // history starts (l5dh_window_forget); the query's status word
+  struct Window {
+    struct Slot {
+      DevBuf row_off, entries, totals;
+      uint32_t count = 0;
+      uint64_t seq = 0, n_entries = 0;
+    };
+    uint32_t slots = 0, filled = 0, head = 0;  // head: the slot the next push writes
+    uint64_t pushes = 0;
+    std::unique_ptr<Slot[]> slot;
+    DevBuf born, status;
+    uint32_t born_n = 0;
+  };
+  std::unique_ptr<Window> win;  // (freed after ~l5dh_ctx has drained the stream, as every device buffer)
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params

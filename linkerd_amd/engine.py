@@ -916,4 +916,6 @@ class HistogramEngine:
         return ms.value, n.value
 
     def kernel_times(self, reset: bool = False) -> dict:
-        return {name: self.kernel_time(k, reset) for k, name in enumerate(N.KERNEL_NAMES)}
+        """The engine's own timed phases (the ids below K_WINDOW; window.Window.kernel_time
+        reads the sliding window's)."""
+        return {name: self.kernel_time(k, reset) for k, name in enumerate(N.KERNEL_NAMES[:N.K_WINDOW])}

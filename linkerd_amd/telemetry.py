@@ -87,6 +87,8 @@ class StatEngine:
         self.quantile_q: Optional[np.ndarray] = None
         self.quantile_labels: Optional[List[str]] = None
         self.quantile_values: Optional[np.ndarray] = None
+        # the sliding window over ended intervals (enable_window): a window.Window of the engine
+        self.window = None
 
     # registry (MetricsTree.mkStat assigns the id; MetricsTree.prune releases it)
     def register(self) -> int:
@@ -110,6 +112,8 @@ class StatEngine:
             self.le_sums[sid] = 0
         if self.quantile_q is not None:
             self.quantile_values[sid] = 0
+        if self.window is not None:  # the id's kept intervals end with its Stat too
+            self.window.forget(sid)
         with self._lock:
             self._free.append(sid)
 
@@ -125,7 +129,8 @@ class StatEngine:
         import_sparse, so they cost what the data costs, not 7192 B per series), the ids
         held by Stats stay valid, and register() succeeds again.  The lifetime ``le``
         counters and the last interval's quantile values are kept and extended with zero
-        rows.  Adds from other threads wait for the swap; snapshot calls must not run beside
+        rows; a sliding window moves to the new engine as it is (Window.move_to: no copy), its
+        new ids reading as empty.  Adds from other threads wait for the swap; snapshot calls must not run beside
         it.  Tunables set on the old engine (HistogramEngine.set_param) are not carried over."""
         capacity = int(capacity)
         self.flush()
@@ -139,6 +144,8 @@ class StatEngine:
             try:
                 row_off, entries, totals = old.export_sparse(first=0, count=self._next, reset=True)
                 new.import_sparse(row_off, entries, totals, first=0)
+                if self.window is not None:
+                    self.window.move_to(new)
             except Exception:
                 new.close()
                 raise
@@ -185,7 +192,8 @@ class StatEngine:
         free list, the ``le`` cuts, labels and lifetime counters, and the configured
         quantiles with the last interval's values (``quantile_q`` is empty when
         enable_quantiles was not called).  ``reset`` ends the interval here (what a process
-        does before it stops)."""
+        does before it stops).  The sliding window (enable_window) is not carried: its kept
+        intervals stay on the device and end with the process."""
         self.flush()
         with self._lock:
             n = self._next
@@ -208,7 +216,8 @@ class StatEngine:
         """Take over a checkpoint: on a fresh StatEngine (no id handed out yet) of at least
         the checkpoint's ids.  Afterwards the engine reports what the checkpointed one
         did, and register() continues where it stopped.  A checkpoint written before the
-        configured quantiles existed (no ``quantile_q``) restores with them off."""
+        configured quantiles existed (no ``quantile_q``) restores with them off.  A checkpoint
+        holds no sliding window: enable_window starts an empty one."""
         from . import _native as N
         n = int(np.asarray(ckpt["next"]).reshape(-1)[0])
         with self._lock:
@@ -378,6 +387,46 @@ class StatEngine:
             self.quantile_values = self.engine.quantiles(self.quantile_q, first=0, count=self.capacity, reset=False)
             return self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=True,
                                          with_series=True, accumulate_into=(self.le_buckets, self.le_sums))[2]
+
+
+    # exact sliding-window summaries over the last W ended intervals
+    def enable_window(self, slots: int) -> None:
+        """Keep the last ``slots`` (1..64) ended intervals on the device (window.Window), fed
+        by push_window and read by window_summaries.  Calling it again starts anew."""
+        from .window import Window
+        if self.window is not None:
+            self.window.close()
+            self.window = None
+        self.window = Window(self.engine, slots)
+
+    def push_window(self) -> np.ndarray:
+        """snapshot_all(reset=True) whose interval is also kept in the window's next slot,
+        from ONE engine call.  With enable_le / enable_quantiles on, every staging lock is
+        held (as snapshot_all_quantiles holds them) over the engine calls -- the quantiles
+        and the ``le`` buckets without a reset, then the push -- so no add can fall between
+        them and all of them see exactly the same samples."""
+        if self.window is None:
+            raise RuntimeError("push_window needs enable_window(slots) first")
+        if self.le_cuts is None and self.quantile_q is None:
+            self.flush()
+            return self.window.push(self.capacity, with_series=True)
+        with self._staging_held():
+            if self.quantile_q is not None:
+                self.quantile_values = self.engine.quantiles(self.quantile_q, first=0, count=self.capacity, reset=False)
+            if self.le_cuts is not None:
+                self.engine.le_counts(self.le_cuts, first=0, count=self.capacity, reset=False,
+                                      accumulate_into=(self.le_buckets, self.le_sums))
+            return self.window.push(self.capacity, with_series=True)
+
+    def window_summaries(self, last: int, include_open: bool = False) -> np.ndarray:
+        """Summaries of every series over the ``last`` most recent pushed intervals (+ the open
+        one with ``include_open``, after flushing every thread's staged adds): what each Stat
+        would report had it received all their samples.  Nothing is reset."""
+        if self.window is None:
+            raise RuntimeError("window_summaries needs enable_window(slots) first")
+        if include_open:
+            self.flush()
+        return self.window.summaries(last, first=0, count=self.capacity, include_open=include_open)
 
 
 class _Staging:
@@ -654,6 +703,27 @@ def snapshot_histograms_quantiles(tree: MetricsTree, engine: StatEngine) -> int:
     the same interval -- and, with enable_le, the lifetime `le` counters fed by it.  Returns
     the number of Stats updated."""
     return _set_snapshots(tree, engine.snapshot_all_quantiles)
+
+
+def snapshot_histograms_window(tree: MetricsTree, engine: StatEngine) -> int:
+    """snapshot_histograms whose interval is also kept in the engine's sliding window
+    (StatEngine.enable_window) -- and, with enable_le / enable_quantiles, feeds those from
+    the same samples.  The tick of a process that answers "p99 over the last five minutes".
+    Returns the number of Stats updated."""
+    return _set_snapshots(tree, lambda reset: engine.push_window())
+
+
+def window_stats(tree: MetricsTree, engine: StatEngine, last: int, include_open: bool = False) -> dict:
+    """{Stat: HistogramSummary} over the ``last`` most recent pushed intervals (+ the open
+    one with ``include_open``), for the Stats of ``tree`` that have a series id.  Nothing is
+    reset and no Stat's snapshottedSummary changes.  The reference has no such query."""
+    summaries = engine.window_summaries(last, include_open=include_open)
+    out = {}
+    for _, t in tree.walk():
+        m = t.metric
+        if isinstance(m, Metric.Stat) and m.series_id is not None:
+            out[m] = HistogramSummary.from_record(summaries[m.series_id])
+    return out
 
 
 def top_stats(tree: MetricsTree, engine: StatEngine, k: int, by="p99", order: str = "largest", min_count: int = 1,
