@@ -62,7 +62,7 @@ int merge_export(l5dh_ctx* c, int mode) {
 // destination rank, the non-empty buckets of its slice plus the words per row --
 // and the totals by one int64 reduce-scatter.  A 1-rank communicator skips it (an
 // identity) unless L5DH_PARAM_MERGE_RCCL_1RANK forces it, with the encoding sent to
-// itself through RCCL.  Steps: encode (local, one host wait for the slice sizes),
+// itself through RCCL.  Steps: pack (local: the export's row encodings in row order),
 // sizes (collective: an all-gather of the words-to matrix), receive buffers (local,
 // one host wait), payload (collective).  l5dh_merge_all groups each collective step
 // over its contexts.  The forcing parameter applies to an RCCL communicator only: a
@@ -70,37 +70,28 @@ int merge_export(l5dh_ctx* c, int mode) {
 // copies skip p == q), so it always takes the identity.
 bool merge_skips_collective(const l5dh_ctx* c) { return c->nranks == 1 && (!c->rccl_1rank || c->loopback); }
 
-int merge_encode_step(l5dh_ctx* c) {
+int merge_pack_step(l5dh_ctx* c) {
   const uint32_t per = merge_per(c);
   const uint32_t Sp = per * (uint32_t)c->nranks;
   const int W = c->nranks;
   int r;
   KTimer kt(c, L5DH_K_MERGE);
   c->m_tmp_bytes = 0;  // (the scans of every slice fit the storage of this, the longest one)
-  HIPCHK(c, merge_count(nullptr, Sp, nullptr, nullptr, nullptr, &c->m_tmp_bytes, c->stream));
+  HIPCHK(c, merge_count(Sp, nullptr, nullptr, nullptr, &c->m_tmp_bytes, c->stream));
   if ((r = ensure(c, c->m_words, ((size_t)Sp + 1) * 4)) || (r = ensure(c, c->m_offs, ((size_t)Sp + 1) * 8)) ||
       (r = ensure(c, c->m_tmp, c->m_tmp_bytes)) || (r = ensure(c, c->m_sizes, (size_t)W * W * 8)))
     return r;
   uint32_t* words = c->m_words.as<uint32_t>();
   uint64_t* offs = c->m_offs.as<uint64_t>();
-  HIPCHK(c, merge_count(nullptr, Sp, words, offs, c->m_tmp.p, &c->m_tmp_bytes, c->stream));  // (words: the export's)
+  HIPCHK(c, merge_count(Sp, words, offs, c->m_tmp.p, &c->m_tmp_bytes, c->stream));  // (words: the export's)
   // this rank's row of the size matrix (for the all-gather) written on the device: the
   // slice sizes reach the host with the matrix, in the receive step's one host wait
   HIPCHK(c, merge_sizes_row(offs, per, W, c->m_sizes.as<uint64_t>() + (size_t)c->rank * W, c->stream));
-  size_t cap = c->m_unpacked_words;  // the packed encoding is no larger than the unpacked one
-  if (!c->m_sparse) {  // (dense rows encoded: the exact size, one host wait)
-    uint64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, offs + Sp, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    cap = total;
-  }
-  if ((r = ensure(c, c->m_enc, cap * 4 + 16))) return r;
-  if (c->m_sparse)  // the export's row encodings packed in row order (one contiguous slice per destination)
-    HIPCHK(c, merge_pack(c->m_unpacked.as<const uint32_t>(), c->m_roff.as<const uint32_t>(), offs,
-                         (uint32_t)std::min<size_t>(Sp, c->S), c->m_enc.as<uint32_t>(), c->stream));
-  else
-    HIPCHK(c, merge_encode(c->merge_counts.as<const int32_t>(), Sp, offs,
-                           c->m_enc.as<uint32_t>(), c->stream));
+  // (the packed encoding is no larger than the unpacked one)
+  if ((r = ensure(c, c->m_enc, c->m_unpacked_words * 4 + 16))) return r;
+  // the export's row encodings packed in row order (one contiguous slice per destination)
+  HIPCHK(c, merge_pack(c->m_unpacked.as<const uint32_t>(), c->m_roff.as<const uint32_t>(), offs,
+                       (uint32_t)std::min<size_t>(Sp, c->S), c->m_enc.as<uint32_t>(), c->stream));
   c->m_dense_bytes = (uint64_t)Sp * (NB * 4 + 8);
   return 0;
 }
@@ -279,8 +270,9 @@ int loop_collectives(l5dh_ctx** cs, int n, int mode) {
     }
     return sync_all(cs, n);
   }
+  if (merge_skips_collective(cs[0])) return 0;  // one rank: merge_finish's identity over the dense export
   for (int i = 0; i < n; ++i)
-    if ((r = merge_encode_step(cs[i]))) return r;
+    if ((r = merge_pack_step(cs[i]))) return r;
   if ((r = sync_all(cs, n))) return r;
   {  // all-gather of the size rows: one copy launch per destination
     for (int j = 0; j < n; ++j) {
@@ -343,7 +335,7 @@ int merge_collectives(l5dh_ctx** cs, int n, int mode) {
   if (merge_skips_collective(cs[0])) return 0;
   for (int i = 0; i < n; ++i) {
     hipSetDevice(cs[i]->device);
-    if ((r = merge_encode_step(cs[i]))) return r;
+    if ((r = merge_pack_step(cs[i]))) return r;
   }
   NCCLCHK(cs[0], ncclGroupStart());
   for (int i = 0; i < n && !r; ++i) {

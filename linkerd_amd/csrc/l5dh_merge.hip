@@ -10,8 +10,10 @@
 // sources are added in rank order -- integer sums, bit-exact), writes the summed
 // dense row and summarizes it in the same pass.
 //
-//   k_mcount   words per row
-//   k_menc     the rows' entries at their exclusive word offsets
+// The encoding itself is written by the export (row_encode in l5dh_device.hpp, the
+// accumulate kernels of l5dh_snapshot.hip), along with the words per row.
+//
+//   k_mpack    the export's row encodings packed in row order
 //   k_mdecode  summed rows of this rank's slice from every source + HistogramSummary
 //   k_scan_*   u32 word counts -> u64 exclusive offsets (tile sums, one-workgroup
 //              scan of the tile sums, tile scans)
@@ -24,42 +26,6 @@ namespace l5dh {
 namespace {
 
 constexpr uint32_t CMAX = MERGE_CMAX;  // count field; CMAX marks an escaped count
-
-__global__ __launch_bounds__(256) void k_mcount(const int32_t* __restrict__ rows, uint32_t nrows,
-                                                uint32_t* __restrict__ words) {
-  const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= nrows) return;
-  const int lane = lane_id();
-  const int32_t* row = rows + (size_t)r * NB;
-  uint32_t w = 0;
-  for (int b = lane; b < NB; b += 64) {
-    const uint32_t c = (uint32_t)row[b];
-    w += (c != 0u) + (c >= CMAX);
-  }
-  w = (uint32_t)wave_sum((uint64_t)w);
-  if (lane == 0) words[r] = w;
-}
-
-__global__ __launch_bounds__(256) void k_menc(const int32_t* __restrict__ rows, uint32_t nrows,
-                                              const uint64_t* __restrict__ offs, uint32_t* __restrict__ enc) {
-  const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= nrows) return;
-  const int lane = lane_id();
-  const int32_t* row = rows + (size_t)r * NB;
-  uint64_t at = offs[r];
-  for (int b0 = 0; b0 < NB; b0 += 64) {  // 64 buckets per step, compacted by ballots
-    const int b = b0 + lane;
-    const uint32_t c = b < NB ? (uint32_t)row[b] : 0u;
-    const bool nz = c != 0u, esc = c >= CMAX;
-    const unsigned long long mn = __ballot(nz), me = __ballot(esc);
-    const uint32_t pos = mask_below(mn) + mask_below(me);
-    if (nz) {
-      enc[at + pos] = ((uint32_t)b << 21) | (esc ? CMAX : c);
-      if (esc) enc[at + pos + 1] = c;
-    }
-    at += (uint64_t)(__popcll(mn) + __popcll(me));
-  }
-}
 
 // The sparse export's rows (encoded at their tiles' places by the accumulate kernels)
 // packed in row order.  The 16 rows of a half-tile are contiguous in the unpacked
@@ -367,23 +333,15 @@ hipError_t merge_loop_sum_i64(const int64_t* const* srcs, int n, int64_t* dst, s
   return loop_sum(srcs, n, dst, count, st);
 }
 
-hipError_t merge_count(const int32_t* rows, uint32_t nrows, uint32_t* words, uint64_t* offs, void* tmp,
-                       size_t* tmp_bytes, hipStream_t st) {
+hipError_t merge_count(uint32_t nrows, uint32_t* words, uint64_t* offs, void* tmp, size_t* tmp_bytes,
+                       hipStream_t st) {
   if (!tmp) {  // size query of the scan's temporary storage
     *tmp_bytes = scan_tmp_bytes(nrows + 1);
     return hipSuccess;
   }
-  // rows == nullptr: words[0..nrows) were written by the export (Outputs::words)
-  if (rows && nrows) hipLaunchKernelGGL(k_mcount, dim3((nrows + 3) / 4), dim3(256), 0, st, rows, nrows, words);
   hipError_t e = hipMemsetAsync(words + nrows, 0, 4, st);  // offs[nrows] = the total
   if (e != hipSuccess) return e;
   return exclusive_scan_u32_u64(words, nrows + 1, offs, tmp, st);
-}
-
-hipError_t merge_encode(const int32_t* rows, uint32_t nrows, const uint64_t* offs, uint32_t* enc, hipStream_t st) {
-  if (nrows == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_menc, dim3((nrows + 3) / 4), dim3(256), 0, st, rows, nrows, offs, enc);
-  return hipGetLastError();
 }
 
 hipError_t merge_pack(const uint32_t* src, const uint32_t* roff, const uint64_t* offs, uint32_t nrows, uint32_t* enc,

@@ -15,12 +15,11 @@ struct MergeRecv {  // the encodings of this rank's row slice from every source 
   int n;                  // sources (<= MERGE_MAX_RANKS)
 };
 
-// words[r] = entry words of row r (words needs nrows + 1 slots; rows == nullptr: already
-// there, from the export), offs[0..nrows] their exclusive prefix (offs[nrows] = the
-// total).  tmp == nullptr: *tmp_bytes receives the scan's temporary storage size.
-hipError_t merge_count(const int32_t* rows, uint32_t nrows, uint32_t* words, uint64_t* offs, void* tmp,
-                       size_t* tmp_bytes, hipStream_t st);
-hipError_t merge_encode(const int32_t* rows, uint32_t nrows, const uint64_t* offs, uint32_t* enc, hipStream_t st);
+// words[r] = entry words of row r (written by the export; words needs nrows + 1 slots),
+// offs[0..nrows] their exclusive prefix (offs[nrows] = the total).  tmp == nullptr:
+// *tmp_bytes receives the scan's temporary storage size.
+hipError_t merge_count(uint32_t nrows, uint32_t* words, uint64_t* offs, void* tmp, size_t* tmp_bytes,
+                       hipStream_t st);
 // the sparse export's row encodings (row r at src + roff[r]; the 16 rows of a half-tile back
 // to back) packed at offs[r] (offs[nrows] = the total)
 hipError_t merge_pack(const uint32_t* src, const uint32_t* roff, const uint64_t* offs, uint32_t nrows, uint32_t* enc,

@@ -387,7 +387,7 @@ int do_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_
   int r = live_begin(c);
   if (r) return r;
   size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(nullptr, count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  HIPCHK(c, merge_count(count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
   if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
       (r = ensure(c, c->xs_tmp, tmp_bytes)))
     return r;
@@ -395,7 +395,7 @@ int do_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_
   {
     KTimer kt(c, L5DH_K_HOT);
     HIPCHK(c, export_sparse_count(state(c), first, count, c->xs_cnt.as<uint32_t>(), c->stream));
-    HIPCHK(c, merge_count(nullptr, count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
+    HIPCHK(c, merge_count(count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
   }
   // the entry count: one host wait, before anything of the caller's is written
   uint64_t total = 0;
@@ -470,7 +470,7 @@ int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, co
       return r;
   }
   size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(nullptr, (uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  HIPCHK(c, merge_count((uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
   if ((r = ensure(c, c->rd_len, (n + 1) * 4)) || (r = ensure(c, c->rd_offs, (n + 1) * 8)) ||
       (r = ensure(c, c->rd_flags, RF_WORDS * 4)) || (r = ensure(c, c->rd_tmp, tmp_bytes)))
     return r;
@@ -480,7 +480,7 @@ int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, co
     KTimer kt(c, L5DH_K_HOT);
     HIPCHK(c, hipMemsetAsync(flags, 0xFF, RF_WORDS * 4, c->stream));
     HIPCHK(c, render_lengths(nm, (uint32_t)n, (uint32_t)nvalues, rows, c->rd_len.as<uint32_t>(), flags, c->stream));
-    HIPCHK(c, merge_count(nullptr, (uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
+    HIPCHK(c, merge_count((uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
   }
   // the device's findings and the text's length: one host wait, before anything is written
   uint32_t hf[RF_WORDS];
@@ -599,7 +599,7 @@ int do_render_influx(l5dh_ctx* c, InfluxRows r, size_t n, uint8_t* out, size_t c
       return rc;
   }
   size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(nullptr, (uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  HIPCHK(c, merge_count((uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
   if ((rc = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT)) || (rc = ensure(c, c->rd_len, (n + 1) * 4)) ||
       (rc = ensure(c, c->rd_offs, (n + 1) * 8)) || (rc = ensure(c, c->ifx_flags, IF_WORDS * 4)) ||
       (rc = ensure(c, c->rd_tmp, tmp_bytes)))
@@ -611,7 +611,7 @@ int do_render_influx(l5dh_ctx* c, InfluxRows r, size_t n, uint8_t* out, size_t c
     KTimer kt(c, L5DH_K_HOT);
     HIPCHK(c, hipMemsetAsync(flags, 0xFF, IF_WORDS * 4, c->stream));
     HIPCHK(c, influx_lengths(r, (uint32_t)n, c->rd_len.as<uint32_t>(), flags, c->stream));
-    HIPCHK(c, merge_count(nullptr, (uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
+    HIPCHK(c, merge_count((uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
   }
   // the device's findings and the text's length: one host wait, before anything is written
   uint32_t hf[IF_WORDS];

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(64 * RU_FIN_WAVES) void k_ru_finish(RollupWork w, T
 
 size_t rollup_tmp_bytes(uint32_t G) {
   size_t bytes = 0;
-  merge_count(nullptr, G + 1, nullptr, nullptr, nullptr, &bytes, nullptr);
+  merge_count(G + 1, nullptr, nullptr, nullptr, &bytes, nullptr);
   return bytes;
 }
 

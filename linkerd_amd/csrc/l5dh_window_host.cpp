@@ -37,7 +37,7 @@ int do_window_push(l5dh_ctx* c, uint32_t count, l5dh_summary* series_out) {
   uint64_t* offs = nullptr;
   if (count) {
     size_t tmp_bytes = 0;
-    HIPCHK(c, merge_count(nullptr, count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+    HIPCHK(c, merge_count(count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
     if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
         (r = ensure(c, c->xs_tmp, tmp_bytes)))
       return r;
@@ -45,7 +45,7 @@ int do_window_push(l5dh_ctx* c, uint32_t count, l5dh_summary* series_out) {
     {
       KTimer kt(c, L5DH_K_HOT);
       HIPCHK(c, export_sparse_count(state(c), 0, count, c->xs_cnt.as<uint32_t>(), c->stream));
-      HIPCHK(c, merge_count(nullptr, count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
+      HIPCHK(c, merge_count(count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
     }
     // the entry count: the one host wait before the slot's buffers are sized
     HIPCHK(c, hipMemcpyAsync(&total, offs + count, 8, hipMemcpyDeviceToHost, c->stream));
