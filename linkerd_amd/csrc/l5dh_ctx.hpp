@@ -157,12 +157,14 @@ struct l5dh_ctx {
   // tiles' flags and list; the export's row counts, offsets, scan scratch and staged entries
   DevBuf imp_status, imp_series, imp_off, imp_entries, imp_tflag, imp_list;
   DevBuf xs_cnt, xs_offs, xs_tmp, xs_entries;
-  // the device renderer (l5dh_render.hip): staged names, values and output, the passes' scratch
+  // the device renderers (l5dh_render.hip, l5dh_influx.hip; one call at a time uses them): staged
+  // names, values and output; the two passes' scratch -- row lengths, their scan's offsets and
+  // scratch, the rows' slots (rd_avg) and the flag words of either renderer (rd_flags)
   DevBuf rd_index, rd_koff, rd_kbytes, rd_loff, rd_lbytes, rd_vals, rd_sums, rd_le, rd_out;
   DevBuf rd_len, rd_offs, rd_avg, rd_flags, rd_tmp;
-  DevBuf rd_kinds, rd_counters, rd_gauges;  // the JSON and scalar blocks' staged kinds and values
-  // the InfluxDB renderer (l5dh_influx.hip): what its table has beyond the arrays staged above, and its flag words
-  DevBuf ifx_line, ifx_field, ifx_hoff, ifx_hbytes, ifx_toff, ifx_tbytes, ifx_host, ifx_flags;
+  DevBuf rd_kinds, rd_counters, rd_gauges;  // the staged kinds and values of the JSON, scalar and InfluxDB calls
+  // the InfluxDB renderer: what its table has beyond the arrays staged above
+  DevBuf ifx_line, ifx_field, ifx_hoff, ifx_hbytes, ifx_toff, ifx_tbytes, ifx_host;
   // the sliding window (l5dh_window_host.cpp): a ring of ended intervals, each slot the CSR of
   // one sparse export (row_off [count + 1], 8-byte entries, totals [count]) with the series
   // it covers and its push number; born [born_n] u64: the push number at which a series'
@@ -308,6 +310,30 @@ int fetch_small(l5dh_ctx* c, const T* p, size_t n, T* host_dst) {
     return 0;
   }
   HIPCHK(c, hipMemcpyAsync(host_dst, p, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  return sync_stream(c);
+}
+
+// ---- count, scan, total: the step the sparse export, the window push and the text passes
+// share.  Sizes cnt [n + 1] u32, offs [n + 1] u64 and the scan's scratch; then, in one
+// L5DH_K_HOT scope, runs count(cnt) -- the caller's launches that fill cnt[0 .. n) -- and the
+// fleet merge's exclusive scan, which leaves offs[n] the total.  total non-null: read back
+// here, with a host wait of its own; null: the caller reads offs[n] with whatever else
+// shares its wait.
+template <class Count>
+int count_scan(l5dh_ctx* c, uint32_t n, DevBuf& cnt, DevBuf& offs, DevBuf& tmp, Count&& count, uint64_t* total = nullptr) {
+  int r;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, merge_count(n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
+  if ((r = ensure(c, cnt, ((size_t)n + 1) * 4)) || (r = ensure(c, offs, ((size_t)n + 1) * 8)) ||
+      (r = ensure(c, tmp, tmp_bytes)))
+    return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    HIPCHK(c, count(cnt.as<uint32_t>()));
+    HIPCHK(c, merge_count(n, cnt.as<uint32_t>(), offs.as<uint64_t>(), tmp.p, &tmp_bytes, c->stream));
+  }
+  if (!total) return 0;
+  HIPCHK(c, hipMemcpyAsync(total, offs.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
   return sync_stream(c);
 }
 

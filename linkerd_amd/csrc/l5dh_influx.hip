@@ -7,8 +7,8 @@
 // 10^5 fields is 10^5 rows like any others.
 //
 //   k_ifx_len    a lane per row: checks the row (kind, field, index, line, offsets, piece
-//                lengths), formats its gauge or avg once into the row's 32-byte slot, and
-//                adds up the row's pieces.
+//                lengths), formats its gauge or avg once into the row's slot, and adds up
+//                the row's pieces.
 //   (scan)       the fleet merge's exclusive u32 -> u64 scan (merge_count): every byte's place.
 //   k_ifx_write  a wave per chunk of 64 consecutive rows (one-wave workgroups striding over
 //                the chunks), a lane per row.  The chunk's bytes are the contiguous range
@@ -16,31 +16,33 @@
 //                lane lays its row out again and writes its own small pieces (`,` `=` the
 //                number, the newline, and every text piece of at most IFX_COOP bytes); the
 //                wave then copies the longer pieces together, one after the other.  A
-//                chunk of at most IFX_STAGE bytes is built in LDS at the destination's
-//                offset within 16 bytes, so it leaves as aligned 16-byte stores between a
-//                byte-wise head and tail; a longer chunk is built by the same code straight
-//                in the output.  Only chunk c's wave writes chunk c's bytes.
+//                chunk of at most TEXT_STAGE bytes is built in LDS at the destination's
+//                offset within 16 bytes and leaves through stage_flush; a longer chunk is
+//                built by the same code straight in the output.  Only chunk c's wave writes
+//                chunk c's bytes.
+//
+// The slot, the stage's way out, `put`, the kinds and the write pass's sizes are
+// l5dh_textout.hpp's, shared with l5dh_render.hip.
 #include "l5dh_device.hpp"
-#include "l5dh_fmt.hpp"
 #include "l5dh_influx.hpp"
+#include "l5dh_textout.hpp"
 
 namespace l5dh {
 namespace {
 
 constexpr uint32_t IFX_ROWS = 64;            // rows of a chunk: a lane each
-constexpr uint32_t IFX_STAGE = 4096;         // bytes of a chunk built in LDS
 constexpr uint32_t IFX_COOP = 48;            // a text piece above this many bytes is copied by the wave together
-constexpr uint32_t IFX_GRID_MAX = 256 * 32;  // one-wave workgroups of the write pass
 constexpr uint32_t AVG_FIELD = 10;           // Summary88's last word: the avg, a double
 
 // A row of a table the length pass found valid, laid out: its pieces and their lengths.
 struct Row {
   bool first, last;     // of its line
-  bool text;            // the value is the slot's text (a gauge, an avg); else the long v
+  bool text;            // the value is the slot's text vtext (a gauge, an avg); else the long v
   uint32_t hlen, tlen;  // the line's head and tail (first rows only, else 0)
   uint32_t klen, vlen;
   uint64_t h0, t0, k0;  // where head, tail and key begin in their byte arrays
   int64_t v;
+  const uint8_t* vtext;
 };
 
 __device__ __forceinline__ void row_layout(const InfluxRows& r, uint32_t n, uint32_t j, Row& R) {
@@ -57,19 +59,26 @@ __device__ __forceinline__ void row_layout(const InfluxRows& r, uint32_t n, uint
     R.t0 = r.tail_off[l];
     R.tlen = (uint32_t)(r.tail_off[l + 1] - R.t0);
   }
-  const uint8_t k = r.kinds[j];
+  const uint8_t k = r.k.kinds[j];
   const uint32_t idx = r.index[j];
   R.v = 0;
+  R.vtext = nullptr;
   if (k == KIND_COUNTER) {
     R.text = false;
-    R.v = r.counters[idx];
+    R.v = r.k.counters[idx];
   } else if (k == KIND_STAT && r.field[j] != AVG_FIELD) {
     R.text = false;
-    R.v = reinterpret_cast<const int64_t*>(r.summaries + idx)[r.field[j]];
+    R.v = reinterpret_cast<const int64_t*>(r.k.summaries + idx)[r.field[j]];
   } else {
     R.text = true;
   }
-  R.vlen = R.text ? r.slot[(size_t)j * RENDER_AVG_SLOT + RENDER_AVG_SLOT - 1] : (uint32_t)fmt::long_digits(R.v);
+  if (R.text) {
+    const SlotText s = slot_read(r.k.slot + (size_t)j * RENDER_AVG_SLOT);
+    R.vtext = s.p;
+    R.vlen = s.n;
+  } else {
+    R.vlen = (uint32_t)fmt::long_digits(R.v);
+  }
 }
 
 // Bytes before the key: head, host and tail, or the comma.
@@ -85,10 +94,10 @@ __global__ __launch_bounds__(256) void k_ifx_len(InfluxRows r, uint32_t n, uint3
                                                  uint32_t* __restrict__ flags) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= n) return;
-  const uint8_t k = r.kinds[j];
+  const uint8_t k = r.k.kinds[j];
   const uint32_t idx = r.index[j], l = r.line[j];
   bool ok = true;
-  if (k != KIND_COUNTER && k != KIND_GAUGE && k != KIND_STAT) {
+  if (!kind_known(k)) {
     atomicMin(flags + IF_KIND, j);
     ok = false;
   } else {
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(256) void k_ifx_len(InfluxRows r, uint32_t n, uint3
       atomicMin(flags + IF_FIELD, j);
       ok = false;
     }
-    if (idx >= (k == KIND_COUNTER ? r.ncounters : (k == KIND_GAUGE ? r.ngauges : r.nsummaries))) {
+    if (idx >= kind_count(r.k, k)) {
       atomicMin(flags + IF_BADIDX, j);
       ok = false;
     }
@@ -131,11 +140,8 @@ __global__ __launch_bounds__(256) void k_ifx_len(InfluxRows r, uint32_t n, uint3
     ok = false;
   }
   if (ok && (k == KIND_GAUGE || (k == KIND_STAT && r.field[j] == AVG_FIELD))) {
-    uint8_t* slot = r.slot + (size_t)j * RENDER_AVG_SLOT;
-    static_assert(fmt::DOUBLE_CHARS < (int)RENDER_AVG_SLOT && fmt::FLOAT_CHARS < (int)RENDER_AVG_SLOT,
-                  "a text and its length share a slot");
-    const int m = k == KIND_GAUGE ? fmt::format_float(r.gauges[idx], slot) : fmt::format_double(r.summaries[idx].avg, slot);
-    slot[RENDER_AVG_SLOT - 1] = (uint8_t)(m < 0 ? 0 : m);
+    uint8_t* slot = r.k.slot + (size_t)j * RENDER_AVG_SLOT;
+    const int m = k == KIND_GAUGE ? slot_write(slot, r.k.gauges[idx]) : slot_write(slot, r.k.summaries[idx].avg);
     if (m < 0) {
       atomicMin(flags + IF_RANGE, j);
       ok = false;
@@ -151,11 +157,6 @@ __global__ __launch_bounds__(256) void k_ifx_len(InfluxRows r, uint32_t n, uint3
 }
 
 // ---- write pass -------------------------------------------------------------------
-__device__ __forceinline__ uint32_t put(uint8_t* dst, uint32_t p, const uint8_t* __restrict__ s, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i) dst[p + i] = s[i];
-  return p + n;
-}
-
 // The wave copies, one after the other, the piece src[0 .. len) of every lane that wants
 // it to dst + at (that lane's values).  Convergent: the whole wave calls it.
 __device__ __forceinline__ void copy_together(uint8_t* dst, bool want, uint32_t at, const uint8_t* src, uint32_t len,
@@ -174,8 +175,8 @@ __device__ __forceinline__ void copy_together(uint8_t* dst, bool want, uint32_t 
 
 // Builds the chunk at dst (LDS or the output: the same code, inlined for each): lane t's row
 // at dst + pos.  Writes inside [pos, pos + row_len) only.
-__device__ __forceinline__ void build_chunk(uint8_t* dst, const InfluxRows& r, const Row& R, bool valid, uint32_t j,
-                                            uint32_t pos, uint32_t lane) {
+__device__ __forceinline__ void build_chunk(uint8_t* dst, const InfluxRows& r, const Row& R, bool valid, uint32_t pos,
+                                            uint32_t lane) {
   const uint32_t host_len = r.host_len, pre = row_pre(R, host_len);
   const uint8_t* head = r.head_bytes + R.h0;
   const uint8_t* tail = r.tail_bytes + R.t0;
@@ -193,7 +194,7 @@ __device__ __forceinline__ void build_chunk(uint8_t* dst, const InfluxRows& r, c
     p += R.klen;
     dst[p++] = '=';
     if (R.text)
-      put(dst, p, r.slot + (size_t)j * RENDER_AVG_SLOT, R.vlen);
+      put(dst, p, R.vtext, R.vlen);
     else
       fmt::format_long(R.v, dst + p);
     if (R.last) dst[p + R.vlen] = '\n';
@@ -207,7 +208,7 @@ __device__ __forceinline__ void build_chunk(uint8_t* dst, const InfluxRows& r, c
 
 __global__ __launch_bounds__(64) void k_ifx_write(InfluxRows r, uint32_t n, const uint64_t* __restrict__ offs,
                                                   uint8_t* __restrict__ out, uint32_t* __restrict__ flags) {
-  __shared__ uint4 stage4[IFX_STAGE / 16 + 1];  // (+16 bytes: the destination's offset within 16)
+  __shared__ uint4 stage4[TEXT_STAGE / 16 + 1];  // (+16 bytes: the destination's offset within 16)
   const uint32_t lane = threadIdx.x;
   const uint32_t nchunks = (n + IFX_ROWS - 1u) / IFX_ROWS;
   for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {  // (wave-uniform)
@@ -231,23 +232,15 @@ __global__ __launch_bounds__(64) void k_ifx_write(InfluxRows r, uint32_t n, cons
       continue;
     }
     uint8_t* gdst = out + o0;
-    if (chunklen <= IFX_STAGE) {
+    if (chunklen <= TEXT_STAGE) {
       const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(gdst) & 15u);
       uint8_t* sdst = reinterpret_cast<uint8_t*>(stage4) + skew;
-      build_chunk(sdst, r, R, valid, j, pos, lane);
+      build_chunk(sdst, r, R, valid, pos, lane);
       __syncthreads();
-      // head up to the first 16-byte boundary of the output, aligned 16-byte body, tail
-      const uint32_t head = min(chunklen, (16u - skew) & 15u);
-      if (lane < head) gdst[lane] = sdst[lane];
-      const uint32_t body = (chunklen - head) >> 4;
-      const uint4* s4 = reinterpret_cast<const uint4*>(sdst + head);  // (skew + head is a multiple of 16, or body == 0)
-      uint4* g4 = reinterpret_cast<uint4*>(gdst + head);
-      for (uint32_t i = lane; i < body; i += 64u) g4[i] = s4[i];
-      const uint32_t done = head + (body << 4);
-      if (done + lane < chunklen) gdst[done + lane] = sdst[done + lane];  // (< 16 bytes)
+      stage_flush(gdst, sdst, chunklen, skew, lane);
       __syncthreads();  // the stage is reused by the next chunk
     } else {
-      build_chunk(gdst, r, R, valid, j, pos, lane);
+      build_chunk(gdst, r, R, valid, pos, lane);
     }
   }
 }
@@ -264,7 +257,7 @@ hipError_t influx_write(const InfluxRows& r, uint32_t n, const uint64_t* offs, u
                         hipStream_t st) {
   if (n == 0) return hipSuccess;
   const uint32_t nchunks = (n + IFX_ROWS - 1u) / IFX_ROWS;
-  hipLaunchKernelGGL(k_ifx_write, dim3(nchunks < IFX_GRID_MAX ? nchunks : IFX_GRID_MAX), dim3(64), 0, st, r, n, offs, out,
+  hipLaunchKernelGGL(k_ifx_write, dim3(nchunks < TEXT_GRID_MAX ? nchunks : TEXT_GRID_MAX), dim3(64), 0, st, r, n, offs, out,
                      flags);
   return hipGetLastError();
 }

@@ -12,8 +12,8 @@ namespace l5dh {
 //   ( first row of l ? head[l] host tail[l] : `,` )  key  `=`  value  ( last row of l ? `\n` : nothing )
 // first: j == 0 or line[j-1] != l; last: j == n-1 or line[j+1] != l.
 struct InfluxRows {
+  KindRows k;                // the rows' kinds [n], the three value arrays and their counts, the slots
   const uint32_t* line;      // [n] non-decreasing, < nlines
-  const uint8_t* kinds;      // [n] KIND_*
   const uint8_t* field;      // [n] a stat row's word of Summary88 (0 .. 10); not read for other kinds
   const uint32_t* index;     // [n] the element of the row's kind's value array
   const uint64_t* key_off;   // [n + 1]
@@ -24,11 +24,6 @@ struct InfluxRows {
   const uint8_t* tail_bytes;
   const uint8_t* host;       // [host_len]
   uint32_t host_len, nlines;
-  const Summary88* summaries;
-  const int64_t* counters;
-  const float* gauges;
-  uint32_t nsummaries, ncounters, ngauges;
-  uint8_t* slot;  // [n][RENDER_AVG_SLOT]: a gauge's or an avg's text, written by the length pass (as KindRows::slot)
 };
 
 // The flag words of a call: each the least row with that finding (0xFFFFFFFF: none).

@@ -386,21 +386,11 @@ int do_export_sparse(l5dh_ctx* c, uint32_t first, uint32_t count, uint64_t* row_
                      size_t* n_entries, int64_t* totals, int reset) {
   int r = live_begin(c);
   if (r) return r;
-  size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count(count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-  if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
-      (r = ensure(c, c->xs_tmp, tmp_bytes)))
-    return r;
-  uint64_t* offs = c->xs_offs.as<uint64_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, export_sparse_count(state(c), first, count, c->xs_cnt.as<uint32_t>(), c->stream));
-    HIPCHK(c, merge_count(count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
-  }
   // the entry count: one host wait, before anything of the caller's is written
   uint64_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(&total, offs + count, 8, hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c))) return r;
+  auto rows = [&](uint32_t* cnt) { return export_sparse_count(state(c), first, count, cnt, c->stream); };
+  if ((r = count_scan(c, count, c->xs_cnt, c->xs_offs, c->xs_tmp, rows, &total))) return r;
+  const uint64_t* offs = c->xs_offs.as<uint64_t>();
   *n_entries = (size_t)total;
   if (!entries) return 0;  // a size query
   if (cap < total)
@@ -431,30 +421,95 @@ int rd_stage_bytes(l5dh_ctx* c, const uint8_t*& bytes, const uint64_t* off, size
   return stage_in(c, bytes, (size_t)last, 1, stage);
 }
 
-// The findings of the passes, in the order the header lists them.
-int rd_findings(l5dh_ctx* c, const uint32_t* f) {
-  const uint32_t none = 0xFFFFFFFFu;
-  if (f[RF_KIND] != none)
-    return fail(c, -EINVAL, "render: the kind of row " + std::to_string(f[RF_KIND]) + " is not one the call prints");
-  if (f[RF_BADIDX] != none)
-    return fail(c, -EINVAL, "render: index of row " + std::to_string(f[RF_BADIDX]) + " is not < nvalues");
-  if (f[RF_BADOFF] != none)
-    return fail(c, -EINVAL, "render: key_off or lab_off descends at row " + std::to_string(f[RF_BADOFF]));
-  if (f[RF_LONG] != none)
-    return fail(c, -EINVAL, "render: key and label text of row " + std::to_string(f[RF_LONG]) + " exceed 2^25 bytes");
-  if (f[RF_RANGE] != none)
-    return fail(c, -ERANGE,
-                "render: avg or gauge of row " + std::to_string(f[RF_RANGE]) +
-                    " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
-  if (f[RF_MISMATCH] != none)
-    return fail(c, -EIO, "internal: the render passes disagree on the length of row " + std::to_string(f[RF_MISMATCH]));
+// A finding of the passes: its flag word holds the least row that has it (0xFFFFFFFF:
+// none), and the call fails with `code` and the text before + the row + after.
+struct Finding {
+  int word, code;
+  const char *before, *after;
+};
+constexpr uint32_t TEXT_FLAG_WORDS = RF_WORDS > IF_WORDS ? RF_WORDS : IF_WORDS;  // rd_flags serves either renderer
+
+// In the order of precedence.
+const Finding RENDER_FINDINGS[] = {
+    {RF_KIND, -EINVAL, "render: the kind of row ", " is not one the call prints"},
+    {RF_BADIDX, -EINVAL, "render: index of row ", " is not < nvalues"},
+    {RF_BADOFF, -EINVAL, "render: key_off or lab_off descends at row ", ""},
+    {RF_LONG, -EINVAL, "render: key and label text of row ", " exceed 2^25 bytes"},
+    {RF_RANGE, -ERANGE, "render: avg or gauge of row ", " is outside +-[2^-64, 2^64), 0, NaN, Infinity"},
+    {RF_MISMATCH, -EIO, "internal: the render passes disagree on the length of row ", ""},
+};
+const Finding INFLUX_FINDINGS[] = {
+    {IF_KIND, -EINVAL, "render_influx: the kind of row ", " is none of the three"},
+    {IF_FIELD, -EINVAL, "render_influx: field of row ", " is above 10"},
+    {IF_BADIDX, -EINVAL, "render_influx: index of row ", " is not < the count of its kind"},
+    {IF_LINE, -EINVAL, "render_influx: line of row ", " is not < nlines, or descends"},
+    {IF_KEYOFF, -EINVAL, "render_influx: key_off descends at row ", ""},
+    {IF_LINEOFF, -EINVAL, "render_influx: head_off or tail_off descends at the line of row ", ""},
+    {IF_LONG, -EINVAL, "render_influx: head, host, tail and key of row ", " exceed 2^25 bytes"},
+    {IF_RANGE, -ERANGE, "render_influx: avg of row ", " is outside +-[2^-64, 2^64), 0, NaN, Infinity"},
+    {IF_MISMATCH, -EIO, "internal: the render_influx passes disagree on the length of row ", ""},
+};
+
+template <size_t N>
+int findings(l5dh_ctx* c, const Finding (&table)[N], const uint32_t* f) {
+  for (const Finding& t : table)
+    if (f[t.word] != 0xFFFFFFFFu) return fail(c, t.code, t.before + std::to_string(f[t.word]) + t.after);
   return 0;
 }
 
-// The passes over n > 0 rows; rows holds device pointers (the caller staged the values).
-// The caller holds the lock and has checked the arguments.  braces: the rows' text is the
+// The two passes of a text over n > 0 rows, from the flag words' 0xFF to the second reading
+// of the findings.  name: the call's, for the messages; lengths(len, flags) and
+// write(offs, out, flags) launch the renderer's passes over inputs the caller staged.  The
+// caller holds the lock and has checked the arguments.  braces: the rows' text is the
 // inside of one JSON object -- it goes from out + 1, `{` goes to out[0] and `}` over the
-// last entry's comma (no entry at all: `{}`), and names' label text is not read.
+// last entry's comma (no entry at all: `{}`).
+template <size_t N, class Lengths, class Write>
+int text_passes(l5dh_ctx* c, const char* name, const Finding (&table)[N], size_t n, Lengths&& lengths, Write&& write,
+                bool braces, uint8_t* out, size_t cap, size_t* len) {
+  int r;
+  if ((r = ensure(c, c->rd_flags, TEXT_FLAG_WORDS * 4))) return r;
+  uint32_t* flags = c->rd_flags.as<uint32_t>();
+  auto count = [&](uint32_t* row_len) {
+    const hipError_t e = hipMemsetAsync(flags, 0xFF, TEXT_FLAG_WORDS * 4, c->stream);
+    return e != hipSuccess ? e : lengths(row_len, flags);
+  };
+  if ((r = count_scan(c, (uint32_t)n, c->rd_len, c->rd_offs, c->rd_tmp, count))) return r;
+  const uint64_t* offs = c->rd_offs.as<uint64_t>();
+  // the device's findings and the text's length: one host wait, before anything is written
+  uint32_t hf[TEXT_FLAG_WORDS];
+  uint64_t total = 0;
+  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
+  if ((r = sync_stream(c)) || (r = findings(c, table, hf))) return r;
+  const uint64_t rows_total = total;
+  if (braces) total = total ? total + 1 : 2;
+  if (len) *len = (size_t)total;
+  if (!out) return 0;  // a size query
+  if (cap < total)
+    return fail(c, -ERANGE,
+                std::string(name) + ": the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
+  StagedOut<uint8_t> o;
+  if ((r = o.begin(c, out, (size_t)total, c->rd_out, 1))) return r;
+  {
+    KTimer kt(c, L5DH_K_HOT);
+    if (rows_total) HIPCHK(c, write(offs, o.dev + (braces ? 1 : 0), flags));
+    if (braces) {
+      HIPCHK(c, hipMemsetAsync(o.dev, '{', 1, c->stream));
+      HIPCHK(c, hipMemsetAsync(o.dev + total - 1, '}', 1, c->stream));
+    }
+  }
+  {
+    KTimer kt(c, L5DH_K_COPY);
+    if ((r = o.end(c))) return r;
+    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((r = sync_stream(c))) return r;
+  return findings(c, table, hf);
+}
+
+// A render call over n > 0 rows: stages the names, then the passes; rows holds device
+// pointers (the caller staged the values).  braces: text_passes', and names' label text is
+// not read.
 template <class Rows>
 int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, const Rows& rows, uint8_t* out, size_t cap,
               size_t* len, bool braces = false) {
@@ -469,48 +524,15 @@ int do_render(l5dh_ctx* c, const l5dh_names* names, size_t n, size_t nvalues, co
         (r = stage_in(c, nm.lab_off, n + 1, 8, c->rd_loff)))
       return r;
   }
-  size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count((uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-  if ((r = ensure(c, c->rd_len, (n + 1) * 4)) || (r = ensure(c, c->rd_offs, (n + 1) * 8)) ||
-      (r = ensure(c, c->rd_flags, RF_WORDS * 4)) || (r = ensure(c, c->rd_tmp, tmp_bytes)))
-    return r;
-  uint32_t* flags = c->rd_flags.as<uint32_t>();
-  uint64_t* offs = c->rd_offs.as<uint64_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, hipMemsetAsync(flags, 0xFF, RF_WORDS * 4, c->stream));
-    HIPCHK(c, render_lengths(nm, (uint32_t)n, (uint32_t)nvalues, rows, c->rd_len.as<uint32_t>(), flags, c->stream));
-    HIPCHK(c, merge_count((uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
-  }
-  // the device's findings and the text's length: one host wait, before anything is written
-  uint32_t hf[RF_WORDS];
-  uint64_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
-  if ((r = sync_stream(c)) || (r = rd_findings(c, hf))) return r;
-  const uint64_t rows_total = total;
-  if (braces) total = total ? total + 1 : 2;
-  if (len) *len = (size_t)total;
-  if (!out) return 0;  // a size query
-  if (cap < total)
-    return fail(c, -ERANGE, "render: the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
-  StagedOut<uint8_t> o;
-  if ((r = o.begin(c, out, (size_t)total, c->rd_out, 1))) return r;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    if (rows_total) HIPCHK(c, render_write(nm, (uint32_t)n, rows, offs, o.dev + (braces ? 1 : 0), flags, c->stream));
-    if (braces) {
-      HIPCHK(c, hipMemsetAsync(o.dev, '{', 1, c->stream));
-      HIPCHK(c, hipMemsetAsync(o.dev + total - 1, '}', 1, c->stream));
-    }
-  }
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = o.end(c))) return r;
-    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  }
-  if ((r = sync_stream(c))) return r;
-  return rd_findings(c, hf);
+  return text_passes(
+      c, "render", RENDER_FINDINGS, n,
+      [&](uint32_t* row_len, uint32_t* flags) {
+        return render_lengths(nm, (uint32_t)n, (uint32_t)nvalues, rows, row_len, flags, c->stream);
+      },
+      [&](const uint64_t* offs, uint8_t* dst, uint32_t* flags) {
+        return render_write(nm, (uint32_t)n, rows, offs, dst, flags, c->stream);
+      },
+      braces, out, cap, len);
 }
 
 // The arguments both render calls share.  0: go on; 1: n == 0, done; negative: an error.
@@ -520,6 +542,18 @@ int rd_check(l5dh_ctx* c, const l5dh_names* names, size_t n, const void* values,
   if (n == 0) return 1;
   if (nvalues == 0 || !values) return fail(c, -EINVAL, "render: no values for the rows");
   if (n > 0xFFFFFFF0ull || nvalues > 0xFFFFFFFFull) return fail(c, -EINVAL, "render: more than 2^32 - 16 rows");
+  return 0;
+}
+
+// The kind arrays of a call (k holds the caller's pointers and counts): staged where they
+// are not used in place, and the n rows' slots sized.  No timer: the caller's.
+int rd_stage_kinds(l5dh_ctx* c, KindRows& k, size_t n) {
+  int r;
+  if ((r = stage_in(c, k.kinds, n, 1, c->rd_kinds)) || (r = stage_in(c, k.summaries, (size_t)k.nsummaries, 8, c->rd_vals)) ||
+      (r = stage_in(c, k.counters, (size_t)k.ncounters, 8, c->rd_counters)) ||
+      (r = stage_in(c, k.gauges, (size_t)k.ngauges, 4, c->rd_gauges)) || (r = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT)))
+    return r;
+  k.slot = c->rd_avg.as<uint8_t>();
   return 0;
 }
 
@@ -540,45 +574,13 @@ int rd_kind_check(l5dh_ctx* c, const l5dh_names* names, const uint8_t* kinds, si
   k.nsummaries = (uint32_t)nsummaries;
   k.ncounters = (uint32_t)ncounters;
   k.ngauges = (uint32_t)ngauges;
-  int r;
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((r = stage_in(c, k.kinds, n, 1, c->rd_kinds)) || (r = stage_in(c, k.summaries, nsummaries, 8, c->rd_vals)) ||
-        (r = stage_in(c, k.counters, ncounters, 8, c->rd_counters)) ||
-        (r = stage_in(c, k.gauges, ngauges, 4, c->rd_gauges)))
-      return r;
-  }
-  if ((r = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT))) return r;
-  k.slot = c->rd_avg.as<uint8_t>();
-  return 0;
+  KTimer kt(c, L5DH_K_COPY);
+  return rd_stage_kinds(c, k, n);
 }
 
 // ---- the InfluxDB renderer -----------------------------------------------------------
-// The findings of its passes, in the order the header lists them.
-int ifx_findings(l5dh_ctx* c, const uint32_t* f) {
-  const uint32_t none = 0xFFFFFFFFu;
-  auto row = [&](int w) { return std::to_string(f[w]); };
-  if (f[IF_KIND] != none) return fail(c, -EINVAL, "render_influx: the kind of row " + row(IF_KIND) + " is none of the three");
-  if (f[IF_FIELD] != none) return fail(c, -EINVAL, "render_influx: field of row " + row(IF_FIELD) + " is above 10");
-  if (f[IF_BADIDX] != none)
-    return fail(c, -EINVAL, "render_influx: index of row " + row(IF_BADIDX) + " is not < the count of its kind");
-  if (f[IF_LINE] != none)
-    return fail(c, -EINVAL, "render_influx: line of row " + row(IF_LINE) + " is not < nlines, or descends");
-  if (f[IF_KEYOFF] != none) return fail(c, -EINVAL, "render_influx: key_off descends at row " + row(IF_KEYOFF));
-  if (f[IF_LINEOFF] != none)
-    return fail(c, -EINVAL, "render_influx: head_off or tail_off descends at the line of row " + row(IF_LINEOFF));
-  if (f[IF_LONG] != none)
-    return fail(c, -EINVAL, "render_influx: head, host, tail and key of row " + row(IF_LONG) + " exceed 2^25 bytes");
-  if (f[IF_RANGE] != none)
-    return fail(c, -ERANGE,
-                "render_influx: avg of row " + row(IF_RANGE) + " is outside +-[2^-64, 2^64), 0, NaN, Infinity");
-  if (f[IF_MISMATCH] != none)
-    return fail(c, -EIO, "internal: the render_influx passes disagree on the length of row " + row(IF_MISMATCH));
-  return 0;
-}
-
 // The passes over n > 0 rows.  The caller holds the lock and has checked the arguments; r
-// holds the caller's pointers, staged here where they are not used in place.
+// holds the caller's pointers and counts, staged here where they are not used in place.
 int do_render_influx(l5dh_ctx* c, InfluxRows r, size_t n, uint8_t* out, size_t cap, size_t* len) {
   int rc;
   const size_t nl = r.nlines;
@@ -588,55 +590,20 @@ int do_render_influx(l5dh_ctx* c, InfluxRows r, size_t n, uint8_t* out, size_t c
     if ((rc = rd_stage_bytes(c, r.key_bytes, koff, n, c->rd_kbytes)) ||
         (rc = rd_stage_bytes(c, r.head_bytes, hoff, nl, c->ifx_hbytes)) ||
         (rc = rd_stage_bytes(c, r.tail_bytes, toff, nl, c->ifx_tbytes)) ||
-        (rc = stage_in(c, r.line, n, 4, c->ifx_line)) || (rc = stage_in(c, r.kinds, n, 1, c->rd_kinds)) ||
-        (rc = stage_in(c, r.field, n, 1, c->ifx_field)) || (rc = stage_in(c, r.index, n, 4, c->rd_index)) ||
-        (rc = stage_in(c, r.key_off, n + 1, 8, c->rd_koff)) || (rc = stage_in(c, r.head_off, nl + 1, 8, c->ifx_hoff)) ||
-        (rc = stage_in(c, r.tail_off, nl + 1, 8, c->ifx_toff)) ||
+        (rc = stage_in(c, r.line, n, 4, c->ifx_line)) || (rc = stage_in(c, r.field, n, 1, c->ifx_field)) ||
+        (rc = stage_in(c, r.index, n, 4, c->rd_index)) || (rc = stage_in(c, r.key_off, n + 1, 8, c->rd_koff)) ||
+        (rc = stage_in(c, r.head_off, nl + 1, 8, c->ifx_hoff)) || (rc = stage_in(c, r.tail_off, nl + 1, 8, c->ifx_toff)) ||
         (rc = stage_in(c, r.host, (size_t)r.host_len, 1, c->ifx_host)) ||
-        (rc = stage_in(c, r.summaries, (size_t)r.nsummaries, 8, c->rd_vals)) ||
-        (rc = stage_in(c, r.counters, (size_t)r.ncounters, 8, c->rd_counters)) ||
-        (rc = stage_in(c, r.gauges, (size_t)r.ngauges, 4, c->rd_gauges)))
+        (rc = rd_stage_kinds(c, r.k, n)))
       return rc;
   }
-  size_t tmp_bytes = 0;
-  HIPCHK(c, merge_count((uint32_t)n, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-  if ((rc = ensure(c, c->rd_avg, n * RENDER_AVG_SLOT)) || (rc = ensure(c, c->rd_len, (n + 1) * 4)) ||
-      (rc = ensure(c, c->rd_offs, (n + 1) * 8)) || (rc = ensure(c, c->ifx_flags, IF_WORDS * 4)) ||
-      (rc = ensure(c, c->rd_tmp, tmp_bytes)))
-    return rc;
-  r.slot = c->rd_avg.as<uint8_t>();
-  uint32_t* flags = c->ifx_flags.as<uint32_t>();
-  uint64_t* offs = c->rd_offs.as<uint64_t>();
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    HIPCHK(c, hipMemsetAsync(flags, 0xFF, IF_WORDS * 4, c->stream));
-    HIPCHK(c, influx_lengths(r, (uint32_t)n, c->rd_len.as<uint32_t>(), flags, c->stream));
-    HIPCHK(c, merge_count((uint32_t)n, c->rd_len.as<uint32_t>(), offs, c->rd_tmp.p, &tmp_bytes, c->stream));
-  }
-  // the device's findings and the text's length: one host wait, before anything is written
-  uint32_t hf[IF_WORDS];
-  uint64_t total = 0;
-  HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, offs + n, 8, hipMemcpyDeviceToHost, c->stream));
-  if ((rc = sync_stream(c)) || (rc = ifx_findings(c, hf))) return rc;
-  if (len) *len = (size_t)total;
-  if (!out) return 0;  // a size query
-  if (cap < total)
-    return fail(c, -ERANGE,
-                "render_influx: the text takes " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
-  StagedOut<uint8_t> o;
-  if ((rc = o.begin(c, out, (size_t)total, c->rd_out, 1))) return rc;
-  {
-    KTimer kt(c, L5DH_K_HOT);
-    if (total) HIPCHK(c, influx_write(r, (uint32_t)n, offs, o.dev, flags, c->stream));
-  }
-  {
-    KTimer kt(c, L5DH_K_COPY);
-    if ((rc = o.end(c))) return rc;
-    HIPCHK(c, hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, c->stream));
-  }
-  if ((rc = sync_stream(c))) return rc;
-  return ifx_findings(c, hf);
+  return text_passes(
+      c, "render_influx", INFLUX_FINDINGS, n,
+      [&](uint32_t* row_len, uint32_t* flags) { return influx_lengths(r, (uint32_t)n, row_len, flags, c->stream); },
+      [&](const uint64_t* offs, uint8_t* dst, uint32_t* flags) {
+        return influx_write(r, (uint32_t)n, offs, dst, flags, c->stream);
+      },
+      false, out, cap, len);
 }
 
 }  // namespace
@@ -923,8 +890,14 @@ int l5dh_render_influx(l5dh_ctx* c, const l5dh_influx_names* names, size_t n, si
   if (n == 0) return 0;
   static_assert(sizeof(l5dh_summary) == sizeof(Summary88), "l5dh_summary layout");
   InfluxRows r{};
+  r.k.kinds = names->kinds;
+  r.k.summaries = reinterpret_cast<const Summary88*>(summaries);
+  r.k.counters = counters;
+  r.k.gauges = gauges;
+  r.k.nsummaries = (uint32_t)nsummaries;
+  r.k.ncounters = (uint32_t)ncounters;
+  r.k.ngauges = (uint32_t)ngauges;
   r.line = names->line;
-  r.kinds = names->kinds;
   r.field = names->field;
   r.index = names->index;
   r.key_off = names->key_off;
@@ -936,12 +909,6 @@ int l5dh_render_influx(l5dh_ctx* c, const l5dh_influx_names* names, size_t n, si
   r.host = host;
   r.host_len = (uint32_t)host_len;
   r.nlines = (uint32_t)nlines;
-  r.summaries = reinterpret_cast<const Summary88*>(summaries);
-  r.counters = counters;
-  r.gauges = gauges;
-  r.nsummaries = (uint32_t)nsummaries;
-  r.ncounters = (uint32_t)ncounters;
-  r.ngauges = (uint32_t)ngauges;
   return do_render_influx(c, r, n, out, cap, len);
 }
 

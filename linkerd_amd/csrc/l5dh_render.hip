@@ -12,28 +12,30 @@
 // lines is the row's: a JSON stat row has one entry, or eleven when its count is above 0.
 //
 //   k_rd_len    a lane per row: checks the row (kind, index, offsets, name length), formats
-//               its avg or gauge once into the row's 32-byte slot, and adds up the lines' lengths from
+//               its avg or gauge once into the row's slot, and adds up the lines' lengths from
 //               the name lengths and the digit counts.
 //   (scan)      the fleet merge's exclusive u32 -> u64 scan (merge_count).
 //   k_rd_write  a wave per row (one-wave workgroups striding over the rows).  Lane t lays
 //               out line t: a wave scan of the line lengths gives its place, and the lane
 //               writes the line's own small pieces (sfx, braces, ext, numbers).  The wave
 //               then copies key and inner into every line together (their first 64 bytes
-//               from registers).  A row of at most RD_STAGE bytes is built in LDS at the
-//               destination's offset within 16 bytes, so it leaves as aligned 16-byte
-//               stores between a byte-wise head and tail; a longer row is built by the same
-//               code straight in the output.  Only row j's wave writes row j's bytes.
+//               from registers).  A row of at most TEXT_STAGE bytes is built in LDS at the
+//               destination's offset within 16 bytes and leaves through stage_flush; a
+//               longer row is built by the same code straight in the output.  Only row j's
+//               wave writes row j's bytes.
+//
+// The slot, the stage's way out, `put`, the kinds and the write pass's sizes are
+// l5dh_textout.hpp's, shared with l5dh_influx.hip.  A Rows struct of l5dh_render.hpp has
+// its Block here (block_of); render_lengths and render_write are one template each,
+// instantiated below for the five Rows.
 #include "l5dh_device.hpp"
-#include "l5dh_fmt.hpp"
-#include "l5dh_render.hpp"
+#include "l5dh_textout.hpp"
 
 namespace l5dh {
 namespace {
 
-constexpr uint32_t RD_STAGE = 4096;               // bytes of a row built in LDS
 constexpr uint32_t RD_LINES_MAX = LE_MAX + 3;     // K buckets, +Inf, _sum, _count
 static_assert(Q_MAX <= RD_LINES_MAX && 11u <= RD_LINES_MAX, "a block's lines have their places in LDS");
-constexpr uint32_t RD_GRID_MAX = 256 * 32;        // one-wave workgroups of the write pass
 
 enum { NUM_LONG = 0, NUM_ULONG = 1, NUM_TEXT = 2 };
 
@@ -83,12 +85,6 @@ __device__ __forceinline__ uint32_t line_len(uint32_t klen, uint32_t ilen, const
   return n + G::sep_n + num_len(L) + 1u;                           // sep number end
 }
 
-template <class S>
-__device__ __forceinline__ uint32_t put(uint8_t* dst, uint32_t p, const S* s, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i) dst[p + i] = (uint8_t)s[i];
-  return p + n;
-}
-
 // The lane's own pieces of its line at dst + pos: everything but key and inner.  Writes
 // inside [pos, pos + line_len) only, and ends exactly there.
 template <class G>
@@ -122,22 +118,21 @@ __device__ __forceinline__ void line_write(uint8_t* dst, uint32_t pos, uint32_t 
 }
 
 // ---- the blocks ---------------------------------------------------------------------
-// A block has its grammar G; kind_ok(j): row j is of a kind the call prints;
+// A block has its grammar G and K_MAX (its rows' K lies in [1, K_MAX]; 0: they have none);
+// kind_ok(j): row j is of a kind the call prints;
 // values(j, nvalues): the number of values the row indexes; prepare(j, idx): the length pass's own work for
 // the row (false: out of the formatter's domain); nlines(j, idx) and line(j, idx, t, L).
 // Summary: _count, _sum, _avg, then QUANTILES' eight lines (min, p50, .., p9999, max).
 struct SummaryBlock {
   using G = PromGrammar;
+  static constexpr uint32_t K_MAX = 0u;
   SummaryRows r;
   __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
   __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
   __device__ __forceinline__ uint32_t nlines(uint32_t, uint32_t) const { return 11u; }
   // The avg's text.
   __device__ __forceinline__ bool prepare(uint32_t j, uint32_t idx) const {
-    uint8_t* slot = r.avg + (size_t)j * RENDER_AVG_SLOT;
-    const int n = fmt::format_double(r.v[idx].avg, slot);
-    slot[RENDER_AVG_SLOT - 1] = (uint8_t)(n < 0 ? 0 : n);
-    return n >= 0;
+    return slot_write(r.avg + (size_t)j * RENDER_AVG_SLOT, r.v[idx].avg) >= 0;
   }
   __device__ __forceinline__ void line(uint32_t j, uint32_t idx, uint32_t t, Line& L) const {
     // Summary88's words: count, min, max, sum, p50, p90, p95, p99, p9990, p9999
@@ -151,17 +146,18 @@ struct SummaryBlock {
     L.ev = q + 7u * qi;
     L.ev_n = (0x16544331u >> (4u * qi)) & 15u;  // their lengths: 1 3 3 4 4 5 6 1
     L.ev_num = 0;
-    const uint8_t* slot = r.avg + (size_t)j * RENDER_AVG_SLOT;
+    const SlotText avg = slot_read(r.avg + (size_t)j * RENDER_AVG_SLOT);
     L.kind = t == 2 ? NUM_TEXT : NUM_LONG;
     L.v = t == 2 ? 0ull : (uint64_t)reinterpret_cast<const int64_t*>(r.v + idx)[field];
-    L.text = slot;
-    L.text_n = t == 2 ? slot[RENDER_AVG_SLOT - 1] : 0u;
+    L.text = avg.p;
+    L.text_n = t == 2 ? avg.n : 0u;
   }
 };
 
 // Histogram: K `_hist_bucket` lines with le="<label>", the le="+Inf" line, _hist_sum, _hist_count.
 struct LeBlock {
   using G = PromGrammar;
+  static constexpr uint32_t K_MAX = LE_MAX;
   LeRows r;
   __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
   __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
@@ -188,6 +184,7 @@ struct LeBlock {
 // Double.toString -- bytes the host formatted once per call, in global memory.
 struct QuantileBlock {
   using G = PromGrammar;
+  static constexpr uint32_t K_MAX = Q_MAX;
   QuantRows r;
   __device__ __forceinline__ bool kind_ok(uint32_t) const { return true; }
   __device__ __forceinline__ uint32_t values(uint32_t, uint32_t nvalues) const { return nvalues; }
@@ -216,12 +213,9 @@ struct KindBlock {
   KindRows r;
   __device__ __forceinline__ bool kind_ok(uint32_t j, bool stats) const {
     const uint8_t k = r.kinds[j];
-    return k == KIND_COUNTER || k == KIND_GAUGE || (stats && k == KIND_STAT);
+    return kind_known(k) && (stats || k != KIND_STAT);
   }
-  __device__ __forceinline__ uint32_t values(uint32_t j) const {
-    const uint8_t k = r.kinds[j];
-    return k == KIND_COUNTER ? r.ncounters : (k == KIND_GAUGE ? r.ngauges : r.nsummaries);
-  }
+  __device__ __forceinline__ uint32_t values(uint32_t j) const { return kind_count(r, r.kinds[j]); }
   __device__ __forceinline__ bool slot_text(uint32_t j, uint32_t idx, bool quote) const {
     const uint8_t k = r.kinds[j];
     if (k == KIND_COUNTER) return true;
@@ -233,28 +227,28 @@ struct KindBlock {
       uint32_t bits;
       __builtin_memcpy(&bits, &x, 4);
       finite = (bits & 0x7F800000u) != 0x7F800000u;
-      n = fmt::format_float(x, slot + 1);
+      n = slot_write(slot, x);
     } else {
+      if (r.summaries[idx].count <= 0) return true;  // (the avg is printed only above 0: nlines)
       const double x = r.summaries[idx].avg;
       uint64_t bits;
       __builtin_memcpy(&bits, &x, 8);
       finite = (bits & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
-      n = r.summaries[idx].count > 0 ? fmt::format_double(x, slot + 1) : 0;  // (printed only then)
+      n = slot_write(slot, x);
     }
-    // the text stands at slot + 1; a quoted one begins at slot + 0
-    static_assert(fmt::DOUBLE_CHARS + 3 <= (int)RENDER_AVG_SLOT, "text, two quotes and the length share a slot");
-    const bool q = quote && !finite && n > 0;
-    if (q) slot[0] = slot[n + 1] = '"';
-    slot[RENDER_AVG_SLOT - 2] = q ? 0 : 1;  // where the text begins
-    slot[RENDER_AVG_SLOT - 1] = (uint8_t)(n < 0 ? 0 : (q ? n + 2 : n));
+    if (quote && !finite && n > 0) {  // (NaN, Infinity, -Infinity) a byte to the right, between the quotes
+      for (int i = n; i > 0; --i) slot[i] = slot[i - 1];
+      slot[0] = slot[n + 1] = '"';
+      slot[SLOT_LEN] = (uint8_t)(n + 2);
+    }
     return n >= 0;
   }
   __device__ __forceinline__ void slot_line(uint32_t j, Line& L) const {
-    const uint8_t* slot = r.slot + (size_t)j * RENDER_AVG_SLOT;
+    const SlotText s = slot_read(r.slot + (size_t)j * RENDER_AVG_SLOT);
     L.kind = NUM_TEXT;
     L.v = 0ull;
-    L.text = slot + slot[RENDER_AVG_SLOT - 2];
-    L.text_n = slot[RENDER_AVG_SLOT - 1];
+    L.text = s.p;
+    L.text_n = s.n;
   }
   __device__ __forceinline__ void plain(Line& L) const {  // no sfx, no extra label, no number yet
     L.sfx = "";
@@ -275,6 +269,7 @@ struct KindBlock {
 // and, only when count > 0, STAT_FIELDS' nine longs and `.avg`.
 struct JsonBlock {
   using G = JsonGrammar;
+  static constexpr uint32_t K_MAX = 0u;
   KindBlock b;
   __device__ __forceinline__ bool kind_ok(uint32_t j) const { return b.kind_ok(j, true); }
   __device__ __forceinline__ uint32_t values(uint32_t j, uint32_t) const { return b.values(j); }
@@ -306,6 +301,7 @@ struct JsonBlock {
 // The counter and gauge lines of the Prometheus exposition: one line per row.
 struct ScalarBlock {
   using G = PromGrammar;
+  static constexpr uint32_t K_MAX = 0u;
   KindBlock b;
   __device__ __forceinline__ bool kind_ok(uint32_t j) const { return b.kind_ok(j, false); }
   __device__ __forceinline__ uint32_t values(uint32_t j, uint32_t) const { return b.values(j); }
@@ -417,7 +413,7 @@ template <class Block>
 __global__ __launch_bounds__(64) void k_rd_write(RenderNames nm, uint32_t n, Block blk,
                                                  const uint64_t* __restrict__ offs, uint8_t* __restrict__ out,
                                                  uint32_t* __restrict__ flags) {
-  __shared__ uint4 stage4[RD_STAGE / 16 + 1];  // (+16 bytes: the destination's offset within 16)
+  __shared__ uint4 stage4[TEXT_STAGE / 16 + 1];  // (+16 bytes: the destination's offset within 16)
   __shared__ uint32_t lpos[RD_LINES_MAX], ipos[RD_LINES_MAX];
   const uint32_t lane = threadIdx.x;
   for (uint32_t j = blockIdx.x; j < n; j += gridDim.x) {  // (wave-uniform)
@@ -430,22 +426,12 @@ __global__ __launch_bounds__(64) void k_rd_write(RenderNames nm, uint32_t n, Blo
     const uint8_t* inner = nm.lab_bytes + i0;
     uint8_t* gdst = out + o0;
     bool ok;
-    if (rowlen <= RD_STAGE) {
+    if (rowlen <= TEXT_STAGE) {
       const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(gdst) & 15u);
       uint8_t* sdst = reinterpret_cast<uint8_t*>(stage4) + skew;
       ok = build_row(sdst, blk, j, idx, key, klen, inner, ilen, rowlen, lpos, ipos, lane);
       __syncthreads();
-      if (ok) {
-        // head up to the first 16-byte boundary of the output, aligned 16-byte body, tail
-        const uint32_t head = min(rowlen, (16u - skew) & 15u);
-        if (lane < head) gdst[lane] = sdst[lane];
-        const uint32_t body = (rowlen - head) >> 4;
-        const uint4* s4 = reinterpret_cast<const uint4*>(sdst + head);  // (skew + head is a multiple of 16, or body == 0)
-        uint4* g4 = reinterpret_cast<uint4*>(gdst + head);
-        for (uint32_t i = lane; i < body; i += 64u) g4[i] = s4[i];
-        const uint32_t done = head + (body << 4);
-        if (done + lane < rowlen) gdst[done + lane] = sdst[done + lane];  // (< 16 bytes)
-      }
+      if (ok) stage_flush(gdst, sdst, rowlen, skew, lane);
     } else {
       ok = build_row(gdst, blk, j, idx, key, klen, inner, ilen, rowlen, lpos, ipos, lane);
     }
@@ -454,69 +440,48 @@ __global__ __launch_bounds__(64) void k_rd_write(RenderNames nm, uint32_t n, Blo
   }
 }
 
+// ---- Rows to Block ------------------------------------------------------------------
+inline SummaryBlock block_of(const SummaryRows& r) { return {r}; }
+inline LeBlock block_of(const LeRows& r) { return {r}; }
+inline QuantileBlock block_of(const QuantRows& r) { return {r}; }
+inline JsonBlock block_of(const JsonRows& r) { return {KindBlock{r.k}}; }
+inline ScalarBlock block_of(const ScalarRows& r) { return {KindBlock{r.k}}; }
+
 template <class Block>
-hipError_t lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const Block& blk, uint32_t* len, uint32_t* flags,
-                   hipStream_t st) {
+bool k_in_range(const Block& blk) {
+  if constexpr (Block::K_MAX > 0u) return blk.r.K >= 1u && blk.r.K <= Block::K_MAX;
+  return true;
+}
+
+}  // namespace
+
+template <class Rows>
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const Rows& rows, uint32_t* len,
+                          uint32_t* flags, hipStream_t st) {
+  using Block = decltype(block_of(rows));
+  const Block blk = block_of(rows);
+  if (!k_in_range(blk)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_rd_len<Block>, dim3((n + 255u) / 256u), dim3(256), 0, st, nm, n, nvalues, blk, len, flags);
   return hipGetLastError();
 }
 
-template <class Block>
-hipError_t write(const RenderNames& nm, uint32_t n, const Block& blk, const uint64_t* offs, uint8_t* out, uint32_t* flags,
-                 hipStream_t st) {
+template <class Rows>
+hipError_t render_write(const RenderNames& nm, uint32_t n, const Rows& rows, const uint64_t* offs, uint8_t* out,
+                        uint32_t* flags, hipStream_t st) {
+  using Block = decltype(block_of(rows));
+  const Block blk = block_of(rows);
+  if (!k_in_range(blk)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rd_write<Block>, dim3(n < RD_GRID_MAX ? n : RD_GRID_MAX), dim3(64), 0, st, nm, n, blk, offs, out,
+  hipLaunchKernelGGL(k_rd_write<Block>, dim3(n < TEXT_GRID_MAX ? n : TEXT_GRID_MAX), dim3(64), 0, st, nm, n, blk, offs, out,
                      flags);
   return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const SummaryRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st) {
-  return lengths(nm, n, nvalues, SummaryBlock{rows}, len, flags, st);
-}
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const LeRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st) {
-  if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
-  return lengths(nm, n, nvalues, LeBlock{rows}, len, flags, st);
-}
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const QuantRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st) {
-  if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
-  return lengths(nm, n, nvalues, QuantileBlock{rows}, len, flags, st);
-}
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const JsonRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st) {
-  return lengths(nm, n, nvalues, JsonBlock{KindBlock{rows.k}}, len, flags, st);
-}
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const ScalarRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st) {
-  return lengths(nm, n, nvalues, ScalarBlock{KindBlock{rows.k}}, len, flags, st);
-}
-hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st) {
-  return write(nm, n, SummaryBlock{rows}, offs, out, flags, st);
-}
-hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st) {
-  if (rows.K < 1 || rows.K > LE_MAX) return hipErrorInvalidValue;
-  return write(nm, n, LeBlock{rows}, offs, out, flags, st);
-}
-
-hipError_t render_write(const RenderNames& nm, uint32_t n, const QuantRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st) {
-  if (rows.K < 1 || rows.K > Q_MAX) return hipErrorInvalidValue;
-  return write(nm, n, QuantileBlock{rows}, offs, out, flags, st);
-}
-hipError_t render_write(const RenderNames& nm, uint32_t n, const JsonRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st) {
-  return write(nm, n, JsonBlock{KindBlock{rows.k}}, offs, out, flags, st);
-}
-hipError_t render_write(const RenderNames& nm, uint32_t n, const ScalarRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st) {
-  return write(nm, n, ScalarBlock{KindBlock{rows.k}}, offs, out, flags, st);
-}
+#define L5DH_RENDER_ROWS(R)                                                                                             \
+  template hipError_t render_lengths(const RenderNames&, uint32_t, uint32_t, const R&, uint32_t*, uint32_t*, hipStream_t); \
+  template hipError_t render_write(const RenderNames&, uint32_t, const R&, const uint64_t*, uint8_t*, uint32_t*, hipStream_t);
+L5DH_RENDER_ROWS(SummaryRows) L5DH_RENDER_ROWS(LeRows) L5DH_RENDER_ROWS(QuantRows) L5DH_RENDER_ROWS(JsonRows) L5DH_RENDER_ROWS(ScalarRows)
+#undef L5DH_RENDER_ROWS
 
 }  // namespace l5dh

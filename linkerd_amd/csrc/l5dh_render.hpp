@@ -35,7 +35,9 @@ enum {
 };
 // 67 lines (L5DH_LE_MAX cuts) of a name this long, their fixed text and numbers stay below 2^32.
 constexpr uint64_t RENDER_NAME_MAX = 1ull << 25;
-constexpr uint32_t RENDER_AVG_SLOT = 32;  // per row: the avg text (26 bytes at most), its length in the last byte
+// per row: the avg's or the gauge's text (26 bytes at most, 28 between quotes), its length in the
+// last byte (the layout is l5dh_textout.hpp's)
+constexpr uint32_t RENDER_AVG_SLOT = 32;
 
 // The values of a call (device pointers).
 struct SummaryRows {
@@ -69,30 +71,19 @@ struct KindRows {
 struct JsonRows { KindRows k; };    // entries `"key sfx":number,` (the caller writes the braces)
 struct ScalarRows { KindRows k; };  // lines `key[{inner}] number\n`; a stat row is RF_KIND
 
+// Both passes are templates over the Rows struct of the call, instantiated in
+// l5dh_render.hip for the five above; hipErrorInvalidValue: LeRows' K outside [1, LE_MAX],
+// QuantRows' outside [1, Q_MAX].
 // Length pass: len[j] = bytes of row j's block for j < n (a row with a finding: 0, and its
-// flag word is lowered).  flags must hold 0xFFFFFFFF words.
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const SummaryRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st);
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const LeRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st);
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const QuantRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st);
-// (nvalues is not read: the counts are the rows')
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const JsonRows& rows, uint32_t* len,
-                          uint32_t* flags, hipStream_t st);
-hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const ScalarRows& rows, uint32_t* len,
+// flag word is lowered).  flags must hold 0xFFFFFFFF words.  (JsonRows, ScalarRows: nvalues
+// is not read, the counts are the rows'.)
+template <class Rows>
+hipError_t render_lengths(const RenderNames& nm, uint32_t n, uint32_t nvalues, const Rows& rows, uint32_t* len,
                           uint32_t* flags, hipStream_t st);
 // Write pass: row j's block at out + offs[j] (offs: the exclusive prefix of len, offs[n] the
 // total).  Only launched when the length pass raised no flag: it trusts the table.
-hipError_t render_write(const RenderNames& nm, uint32_t n, const SummaryRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st);
-hipError_t render_write(const RenderNames& nm, uint32_t n, const LeRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st);
-hipError_t render_write(const RenderNames& nm, uint32_t n, const QuantRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st);
-hipError_t render_write(const RenderNames& nm, uint32_t n, const JsonRows& rows, const uint64_t* offs, uint8_t* out,
-                        uint32_t* flags, hipStream_t st);
-hipError_t render_write(const RenderNames& nm, uint32_t n, const ScalarRows& rows, const uint64_t* offs, uint8_t* out,
+template <class Rows>
+hipError_t render_write(const RenderNames& nm, uint32_t n, const Rows& rows, const uint64_t* offs, uint8_t* out,
                         uint32_t* flags, hipStream_t st);
 
 }  // namespace l5dh

@@ -36,20 +36,10 @@ int do_window_push(l5dh_ctx* c, uint32_t count, l5dh_summary* series_out) {
   uint64_t total = 0;
   uint64_t* offs = nullptr;
   if (count) {
-    size_t tmp_bytes = 0;
-    HIPCHK(c, merge_count(count, nullptr, nullptr, nullptr, &tmp_bytes, c->stream));
-    if ((r = ensure(c, c->xs_cnt, ((size_t)count + 1) * 4)) || (r = ensure(c, c->xs_offs, ((size_t)count + 1) * 8)) ||
-        (r = ensure(c, c->xs_tmp, tmp_bytes)))
-      return r;
-    offs = c->xs_offs.as<uint64_t>();
-    {
-      KTimer kt(c, L5DH_K_HOT);
-      HIPCHK(c, export_sparse_count(state(c), 0, count, c->xs_cnt.as<uint32_t>(), c->stream));
-      HIPCHK(c, merge_count(count, c->xs_cnt.as<uint32_t>(), offs, c->xs_tmp.p, &tmp_bytes, c->stream));
-    }
     // the entry count: the one host wait before the slot's buffers are sized
-    HIPCHK(c, hipMemcpyAsync(&total, offs + count, 8, hipMemcpyDeviceToHost, c->stream));
-    if ((r = sync_stream(c))) return r;
+    auto rows = [&](uint32_t* cnt) { return export_sparse_count(state(c), 0, count, cnt, c->stream); };
+    if ((r = count_scan(c, count, c->xs_cnt, c->xs_offs, c->xs_tmp, rows, &total))) return r;
+    offs = c->xs_offs.as<uint64_t>();
   }
   // room for the interval: the slot's buffers are reused when large enough, else replaced --
   // after every allocation has succeeded, so a failure leaves the ring as it was

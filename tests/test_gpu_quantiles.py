@@ -345,6 +345,8 @@ def test_render_contract(dense):
                                             out, cap, ctypes.byref(ln))
         return rc, ln.value
     assert raw(qs, 3, buf.data_ptr(), len(want) - 1) == (-errno.ERANGE, len(want))
+    assert eng._lib.l5dh_last_error(eng._ctx).decode() == (
+        f"render: the text takes {len(want)} bytes, cap is {len(want) - 1}")
     assert (buf.cpu().numpy() == GUARD).all()  # nothing was written
     assert raw(qs, 3, buf.data_ptr(), len(want)) == (0, len(want))
     assert buf[:len(want)].cpu().numpy().tobytes() == want

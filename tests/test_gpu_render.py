@@ -198,6 +198,19 @@ def _raw_summaries(eng, table, values, out, cap):
     return rc, ln.value
 
 
+def last_error(eng):
+    """The whole text l5dh_last_error holds for the engine's context."""
+    return eng._lib.l5dh_last_error(eng._ctx).decode()
+
+
+def cap_message(eng, call, want_len):
+    """call(out) into a host buffer one byte short: -ERANGE, and the message names both sizes."""
+    with pytest.raises(N.L5dhError) as ei:
+        call(np.empty(want_len - 1, np.uint8))
+    assert ei.value.code == -errno.ERANGE
+    assert last_error(eng) == f"render: the text takes {want_len} bytes, cap is {want_len - 1}"
+
+
 def test_contract_sizes_and_device_findings(eng, avgs):
     import torch
     n = 70
@@ -205,6 +218,9 @@ def test_contract_sizes_and_device_findings(eng, avgs):
     assert _raw_summaries(eng, table, values, None, 0) == (0, len(want))  # the size query
     buf = torch.full((len(want) + 64,), GUARD, dtype=torch.uint8, device="cuda:0")
     assert _raw_summaries(eng, table, values, buf, len(want) - 1) == (-errno.ERANGE, len(want))
+    assert last_error(eng) == f"render: the text takes {len(want)} bytes, cap is {len(want) - 1}"
+    le_table, le_rows, le_sums, le_labels, le_want = le_case(65, 1, True)
+    cap_message(eng, lambda out: eng.render_le(le_table, le_rows, le_sums, le_labels, out=out), len(le_want))
     assert (buf.cpu().numpy() == GUARD).all()  # nothing was written
     empty = NameTable(None, np.zeros(1, np.uint64), np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint8))
     assert _raw_summaries(eng, empty, values, buf, 64) == (0, 0) and (buf.cpu().numpy() == GUARD).all()
@@ -224,12 +240,14 @@ def test_contract_sizes_and_device_findings(eng, avgs):
     with pytest.raises(N.L5dhError, match="row 37") as ei:
         eng.render_summaries(NameTable(bad, table.key_off, table.key_bytes, table.lab_off, table.lab_bytes), values)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == "render: index of row 37 is not < nvalues"
     # an offset that descends
     off = table.lab_off.copy()
     off[51] = off[50] - 1
     with pytest.raises(N.L5dhError, match="row 50") as ei:
         eng.render_summaries(NameTable(table.index, table.key_off, table.key_bytes, off, table.lab_bytes), values)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == "render: key_off or lab_off descends at row 50"
     # an avg outside the domain: -ERANGE, and l5dh_last_error names the row
     far = values.copy()
     far["avg"][int(table.index[12])] = 2.0 ** 70
@@ -237,6 +255,7 @@ def test_contract_sizes_and_device_findings(eng, avgs):
     with pytest.raises(N.L5dhError, match=f"row {first} ") as ei:
         eng.render_summaries(table, far)
     assert ei.value.code == -errno.ERANGE
+    assert last_error(eng) == f"render: avg or gauge of row {first} is outside +-[2^-64, 2^64), 0, NaN, Infinity"
     assert eng.render_summaries(table, values) == want  # a valid call afterwards succeeds
 
 

@@ -19,7 +19,7 @@ from linkerd_amd.telemetry import (HistogramSummary, MetricsTree, MetricsTreeSta
 from . import influx_cases as IC
 from . import render_cases as C
 from .test_exporters_host import ONE_TWO
-from .test_gpu_render_json import GUARD, _dev, render_guarded
+from .test_gpu_render_json import GUARD, _dev, last_error, render_guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -237,6 +237,7 @@ def test_contract_sizes(eng):
     assert render_influx(eng, table, b"none", *values, out=QUERY) == len(want)
     buf = torch.full((len(want) + 64,), GUARD, dtype=torch.uint8, device="cuda:0")
     assert _raw(eng, table, b"none", *values, buf, len(want) - 1) == (-errno.ERANGE, len(want))
+    assert last_error(eng) == f"render_influx: the text takes {len(want)} bytes, cap is {len(want) - 1}"
     assert (buf.cpu().numpy() == GUARD).all()  # nothing was written
     assert _raw(eng, table, b"none", *values, buf, len(want)) == (0, len(want))
     assert buf.cpu().numpy()[:len(want)].tobytes() == want and (buf.cpu().numpy()[len(want):] == GUARD).all()
@@ -278,10 +279,11 @@ def table_lines(body: bytes) -> int:
 def test_device_findings(eng):
     table, (summ, counters, gauges), want = contract_case()
 
-    def finding(code, row, t=None, s=summ, c=counters, g=gauges):
+    def finding(code, row, message, t=None, s=summ, c=counters, g=gauges):
         with pytest.raises(N.L5dhError, match=f"row {row}( |$)") as ei:
             render_influx(eng, table if t is None else t, "none", s, c, g)
         assert ei.value.code == code
+        assert last_error(eng) == "render_influx: " + message.format(row=row)
         assert render_influx(eng, table, "none", summ, counters, gauges) == want  # a valid call afterwards succeeds
 
     def changed(**arrays):
@@ -294,32 +296,35 @@ def test_device_findings(eng):
     gauge_rows = np.flatnonzero(table.kinds == N.KIND_GAUGE)
     kinds = table.kinds.copy()
     kinds[[37, 50]] = 7
-    finding(-errno.EINVAL, 37, changed(kinds=kinds))
+    finding(-errno.EINVAL, 37, "the kind of row {row} is none of the three", changed(kinds=kinds))
     field = table.field.copy()
     field[stat_rows[[4, 9]]] = 11
-    finding(-errno.EINVAL, stat_rows[4], changed(field=field))
+    finding(-errno.EINVAL, stat_rows[4], "field of row {row} is above 10", changed(field=field))
     # an index at its kind's count: one gauge fewer than the rows name
     top = int(table.index[gauge_rows].max())
-    finding(-errno.EINVAL, min(r for r in gauge_rows if table.index[r] >= top), g=gauges[:top])
-    finding(-errno.EINVAL, stat_rows[0], s=None)  # a kind without values
+    finding(-errno.EINVAL, min(r for r in gauge_rows if table.index[r] >= top),
+            "index of row {row} is not < the count of its kind", g=gauges[:top])
+    finding(-errno.EINVAL, stat_rows[0], "index of row {row} is not < the count of its kind", s=None)  # a kind without values
     line = table.line.copy()
     line[30] = line[29] + 1
     assert line[31] < line[30]
-    finding(-errno.EINVAL, 31, changed(line=line))  # descending
+    finding(-errno.EINVAL, 31, "line of row {row} is not < nlines, or descends", changed(line=line))  # descending
     line = table.line.copy()
     line[40:] = np.maximum(line[40:], table.nlines)
-    finding(-errno.EINVAL, 40, changed(line=line))  # >= nlines
+    finding(-errno.EINVAL, 40, "line of row {row} is not < nlines, or descends", changed(line=line))  # >= nlines
     off = table.key_off.copy()
     off[51] = off[50] - 1
-    finding(-errno.EINVAL, 50, changed(key_off=off))
+    finding(-errno.EINVAL, 50, "key_off descends at row {row}", changed(key_off=off))
     l = int(table.line[45])
     off = table.head_off.copy()
     off[l + 1] = off[l] - 1
-    finding(-errno.EINVAL, int(np.flatnonzero(table.line == l)[0]), changed(head_off=off))
+    finding(-errno.EINVAL, int(np.flatnonzero(table.line == l)[0]),
+            "head_off or tail_off descends at the line of row {row}", changed(head_off=off))
     far = summ.copy()
     avg_rows = stat_rows[table.field[stat_rows] == N.BY_AVG]
     far["avg"][table.index[avg_rows[1]]] = 2.0 ** 70
-    finding(-errno.ERANGE, min(r for r in avg_rows if table.index[r] == table.index[avg_rows[1]]), s=far)
+    finding(-errno.ERANGE, min(r for r in avg_rows if table.index[r] == table.index[avg_rows[1]]),
+            "avg of row {row} is outside +-[2^-64, 2^64), 0, NaN, Infinity", s=far)
     assert _raw(eng, table, b"h" * 65536, summ, counters, gauges, None, 0)[0] == -errno.EINVAL
 
 

@@ -204,6 +204,7 @@ def test_json_contract_sizes(eng):
     assert _raw_json(eng, table, *values, None, 0) == (0, len(want))  # the size query
     buf = torch.full((len(want) + 64,), GUARD, dtype=torch.uint8, device="cuda:0")
     assert _raw_json(eng, table, *values, buf, len(want) - 1) == (-errno.ERANGE, len(want))
+    assert last_error(eng) == f"render: the text takes {len(want)} bytes, cap is {len(want) - 1}"
     assert (buf.cpu().numpy() == GUARD).all()  # nothing was written
     assert _raw_json(eng, table, *values, buf, len(want)) == (0, len(want))
     assert buf.cpu().numpy()[:len(want)].tobytes() == want and (buf.cpu().numpy()[len(want):] == GUARD).all()
@@ -231,6 +232,11 @@ def test_json_output_at_every_skew(eng):
         assert render_guarded(lambda out: render_json(eng, dtab, *dv, out=out), len(want), skew=skew) == want
 
 
+def last_error(eng):
+    """The whole text l5dh_last_error holds for the engine's context."""
+    return eng._lib.l5dh_last_error(eng._ctx).decode()
+
+
 def test_device_findings(eng):
     table, (summ, counters, gauges), want = json_case(70, "perm")
     stat_rows = np.flatnonzero(table.kinds == N.KIND_STAT)
@@ -241,10 +247,12 @@ def test_device_findings(eng):
     with pytest.raises(N.L5dhError, match="row 37 ") as ei:
         render_json(eng, bad, summ, counters, gauges)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == "render: the kind of row 37 is not one the call prints"
     # a stat row in render_scalars
     with pytest.raises(N.L5dhError, match=f"row {stat_rows[0]} ") as ei:
         render_scalars(eng, table, counters, gauges)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == f"render: the kind of row {stat_rows[0]} is not one the call prints"
     # an index at its own kind's count: the gauges are fewer than the other arrays
     j = int(np.flatnonzero(table.kinds == N.KIND_GAUGE)[3])
     few = gauges[:int(table.index[j])]
@@ -252,17 +260,20 @@ def test_device_findings(eng):
     with pytest.raises(N.L5dhError, match=f"row {min(rows)} ") as ei:
         render_json(eng, table, summ, counters, few)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == f"render: index of row {min(rows)} is not < nvalues"
     assert (table.index[table.kinds != N.KIND_GAUGE] >= few.size).any()  # (legal for the other kinds)
     # a kind without values: each of its rows is out of range
     with pytest.raises(N.L5dhError, match=f"row {stat_rows[0]} ") as ei:
         render_json(eng, table, None, counters, gauges)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == f"render: index of row {stat_rows[0]} is not < nvalues"
     # offsets that descend
     off = table.key_off.copy()
     off[51] = off[50] - 1
     with pytest.raises(N.L5dhError, match="row 50") as ei:
         render_json(eng, NameTable(table.index, off, table.key_bytes, None, None, None, table.kinds), summ, counters, gauges)
     assert ei.value.code == -errno.EINVAL
+    assert last_error(eng) == "render: key_off or lab_off descends at row 50"
     # an avg outside the double formatter's domain under a positive count: -ERANGE, the row named
     far = summ.copy()
     k = int(table.index[stat_rows[5]])
@@ -271,6 +282,13 @@ def test_device_findings(eng):
     with pytest.raises(N.L5dhError, match=f"row {first} ") as ei:
         render_json(eng, table, far, counters, gauges)
     assert ei.value.code == -errno.ERANGE
+    assert last_error(eng) == f"render: avg or gauge of row {first} is outside +-[2^-64, 2^64), 0, NaN, Infinity"
+    # the cap too small message of the scalar call
+    one = NameTable.build(["a"], [""], [0], None, [N.KIND_COUNTER])
+    with pytest.raises(N.L5dhError) as ei:
+        render_scalars(eng, one, np.array([-5], np.int64), None, out=np.empty(4, np.uint8))  # `a -5\n`
+    assert ei.value.code == -errno.ERANGE
+    assert last_error(eng) == "render: the text takes 5 bytes, cap is 4"
     far["count"][k] = 0  # not printed: not formatted
     assert len(render_json(eng, table, far, counters, gauges)) > 0
     # (l5dh_format_float covers every float -- FLT_MAX, the least subnormal and 2^70 are
