@@ -10,6 +10,7 @@ Modules:
   _native    ctypes binding of the C-ABI (raises if the HIP library is absent)
   engine     HistogramEngine (one context = one GPU shard)
   telemetry  MetricsTree / Metric.{Counter,Stat,Gauge} / HistogramSummary mirror
+  nametable  what the exporters share: the labelled tree walk, the name tables, a scrape's rows
   prometheus PrometheusTelemeter text export from GPU summaries
   top        /admin/metrics/top.json: the exact top-k Stats, selected on the GPU
   fleet      multi-GPU series sharding and the RCCL fleet merge

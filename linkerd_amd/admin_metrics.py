@@ -24,13 +24,16 @@ from __future__ import annotations
 
 import math
 import threading
-import errno
 from typing import List, Optional, Tuple
 from urllib.parse import parse_qs, urlsplit
 
 import numpy as np
 
+from . import _native as N
 from .javafmt import double_to_string, float_to_string, long_to_string
+from .nametable import (NO_INDEX, NameTable, device_or_host, kind_of, scalar_ordinals, scalar_values,  # noqa: F401
+                        scrape_rows, series_index, utf16_key)
+from .render_json import render_json
 from .telemetry import Metric, MetricsTree, StatEngine, snapshot_histograms
 
 STAT_FIELDS = ("max", "min", "p50", "p90", "p95", "p99", "p9990", "p9999", "sum")
@@ -125,54 +128,36 @@ def flatten_metrics_tree(tree: MetricsTree, prefix: str = "", acc=None) -> List[
     return acc
 
 
-def _utf16_key(s: str):
-    return s.encode("utf-16-be", "surrogatepass")
-
-
 def write_flat_json(tree: MetricsTree, pretty: bool = False) -> str:
     jg = _Gen(pretty)
     jg.start_object()
     flat = flatten_metrics_tree(tree)
     if pretty:
-        flat = sorted(flat, key=lambda kv: _utf16_key(kv[0]))  # Seq.sortBy(_._1): stable, String ordering
+        flat = sorted(flat, key=lambda kv: utf16_key(kv[0]))  # Seq.sortBy(_._1): stable, String ordering
     for name, m in flat:
         _write_metric(jg, name, m)
     jg.end_object()
     return jg.text()
 
 
-def flat_name_table(tree: MetricsTree):
-    """The prometheus.NameTable of write_flat_json's compact document for the device
+def flat_name_table(tree: MetricsTree) -> NameTable:
+    """The NameTable of write_flat_json's compact document for the device
     (render_json.render_json): one row per node that holds a metric, in
     flatten_metrics_tree order, its key the ``a/b/c`` name escaped as json_string escapes
     it (without the quotes), no label text.  A stat's ``index`` is its series id (NO_INDEX
     without one); a counter's or a gauge's is its ordinal among the rows of its kind, the
     order of scalar_values."""
-    from ._native import KIND_COUNTER, KIND_GAUGE, KIND_STAT
-    from .prometheus import NO_INDEX, NameTable
-    keys, index, kinds, metrics = [], [], [], []
-    seen = [0, 0]
+    keys, metrics, kinds = [], [], []
     for name, m in flatten_metrics_tree(tree):
-        if isinstance(m, Metric.Stat):
-            kind, idx = KIND_STAT, NO_INDEX if m.series_id is None else int(m.series_id)
-        elif isinstance(m, (Metric.Counter, Metric.Gauge)):
-            kind = KIND_COUNTER if isinstance(m, Metric.Counter) else KIND_GAUGE
-            idx = seen[kind]
-            seen[kind] += 1
-        else:
-            continue
-        keys.append(json_string(name)[1:-1])
-        index.append(idx)
-        kinds.append(kind)
-        metrics.append(m)
-    return NameTable.build(keys, [""] * len(keys), index, metrics, kinds)
-
-
-def scalar_values(table):
-    """(counters int64, gauges float32) of one scrape: the current values of the counter
-    and gauge rows of a host table, each in the order its rows' ``index`` counts."""
-    from .prometheus import scalar_values as values
-    return values(table)
+        kind = kind_of(m)
+        if kind is not None:
+            keys.append(json_string(name)[1:-1])
+            metrics.append(m)
+            kinds.append(kind)
+    kinds = np.asarray(kinds, np.uint8)
+    index = np.full(kinds.size, NO_INDEX, np.int64)
+    index[kinds == N.KIND_STAT] = series_index(m for m, kind in zip(metrics, kinds) if kind == N.KIND_STAT)
+    return NameTable.build(keys, [""] * len(keys), scalar_ordinals(index, kinds), metrics, kinds)
 
 
 def _write_tree(jg: _Gen, tree: MetricsTree) -> None:
@@ -253,9 +238,6 @@ class AdminMetricsExportTelemeter:
         prints its record; None takes each Stat's snapshotted summary, and a Stat without
         one prints nothing.  The pretty and tree forms and the 404 are the host writers'
         text, as is a document with an avg outside the device formatter's domain."""
-        from ._native import KIND_STAT, L5dhError
-        from .prometheus import NameTable, summary_records
-        from .render_json import render_json
         params = parse_qs(urlsplit(uri).query, keep_blank_values=True)
         q = params["q"][0] if "q" in params else None
         sub = self.metrics.try_resolve(_java_split_slash(q)) if q is not None else self.metrics
@@ -263,31 +245,14 @@ class AdminMetricsExportTelemeter:
             status, media, body = self.handle(uri)
             return status, media, body.encode("utf-8")
         table = names if names is not None and sub is self.metrics else flat_name_table(sub)
-        stat = table.kinds == KIND_STAT
-        if summaries is not None:
-            keep = [j for j, m in enumerate(table.metrics) if not stat[j] or m.series_id is not None]
-            records = summaries
-        else:
-            # the kept Stats' records beside them, in table order: their index is their ordinal
-            snaps = [m.snapshotted_summary if stat[j] else None for j, m in enumerate(table.metrics)]
-            keep = [j for j in range(table.n) if not stat[j] or snaps[j] is not None]
-            shown = [snaps[j] for j in keep if stat[j]]
-            records = summary_records(shown) if shown else None
         counters, gauges = scalar_values(table)
-        if len(keep) != table.n:
-            table = table.take(keep)
-        if summaries is None and table.n:
-            index = table.index.copy()
-            index[table.kinds == KIND_STAT] = np.arange(len(shown), dtype=np.uint32)
-            table = NameTable(index, table.key_off, table.key_bytes, table.lab_off, table.lab_bytes, table.metrics,
-                              table.kinds)
-        try:
-            body = render_json(engine, table, records, counters if counters.size else None,
-                               gauges if gauges.size else None)
-        except L5dhError as e:
-            if e.code != -errno.ERANGE:
-                raise
-            body = write_flat_json(sub, False).encode("utf-8")
+        stat = table.kinds == N.KIND_STAT
+        # the kept Stats' records beside them, in table order (summaries None), or the snapshot's by series id
+        table, records = scrape_rows(table, [m for m, is_stat in zip(table.metrics, stat) if is_stat], summaries,
+                                     np.where(stat, np.cumsum(stat) - 1, -1))
+        body = device_or_host(lambda: render_json(engine, table, records, counters if counters.size else None,
+                                                  gauges if gauges.size else None),
+                              lambda: write_flat_json(sub, False).encode("utf-8"))
         return 200, "application/json", body
 
     # -- snapshot driver -----------------------------------------------------

@@ -15,78 +15,43 @@ reference).
 """
 from __future__ import annotations
 
-import re
+from operator import attrgetter
 from typing import List, Sequence, Tuple
 
+from . import _native as N
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .telemetry import Metric, MetricsTree
-
-_DISALLOWED = re.compile(r"[^a-zA-Z0-9:]")
-ROOT_PREFIX = ("root",)
+from .nametable import device_or_host, escape_key, kind_of, utf16_key, walk  # noqa: F401
+from .render_influx import ROOT_PREFIX, STAT_FIELDS, influx_table, render_influx, scrape_inputs
+from .telemetry import MetricsTree
 
 Tags = Tuple[Tuple[str, str], ...]
-
-
-def escape_key(key: str) -> str:
-    return _DISALLOWED.sub("_", key)
-
-
-def _utf16_key(kv):
-    return kv[0].encode("utf-16-be", "surrogatepass")
+# a Stat's fields: their values of a summary, and per field (key suffix, formatter)
+_stat_values = attrgetter(*(N.SUMMARY_FIELDS[f] for _, f in STAT_FIELDS))
+_STAT_TEXTS = [(sfx, double_to_string if f == N.BY_AVG else long_to_string) for sfx, f in STAT_FIELDS]
 
 
 def format_labels(labels: Sequence[Tuple[str, str]]) -> str:
-    return ",".join(f"{k}={v}" for k, v in sorted(labels, key=_utf16_key))  # stable sortBy(_._1)
-
-
-def _label_exists(tags: Tags, name: str) -> bool:
-    return any(k == name for k, _ in tags)
-
-
-def _rewrite(prefix: Tuple[str, ...], tags: Tags):
-    if len(prefix) == 2 and prefix[0] == "rt" and not _label_exists(tags, "rt"):
-        return ("rt",), tags + (("rt", prefix[1]),)
-    if len(prefix) == 3 and prefix[:2] == ("rt", "service") and not _label_exists(tags, "service"):
-        return ("rt", "service"), tags + (("service", prefix[2]),)
-    if len(prefix) == 3 and prefix[:2] == ("rt", "client") and not _label_exists(tags, "client"):
-        return ("rt", "client"), tags + (("client", prefix[2]),)
-    if len(prefix) == 4 and prefix[:3] == ("rt", "client", "service") and not _label_exists(tags, "service"):
-        return ("rt", "client", "service"), tags + (("service", prefix[3]),)
-    if len(prefix) == 3 and prefix[:2] == ("rt", "server") and not _label_exists(tags, "server"):
-        return ("rt", "server"), tags + (("server", prefix[2]),)
-    return prefix, tags
+    return ",".join(f"{k}={v}" for k, v in sorted(labels, key=lambda kv: utf16_key(kv[0])))  # stable sortBy(_._1)
 
 
 def _fields(name: str, m) -> List[Tuple[str, str]]:
-    if isinstance(m, Metric.Counter):
+    kind = kind_of(m)
+    if kind == N.KIND_COUNTER:
         return [(name, long_to_string(m.get()))]
-    if isinstance(m, Metric.Gauge):
+    if kind == N.KIND_GAUGE:
         return [(name, float_to_string(m.get()))]
-    if isinstance(m, Metric.Stat):
-        s = m.snapshotted_summary
-        if s is None:
-            return []
-        return [(name + "_count", long_to_string(s.count)), (name + "_sum", long_to_string(s.sum)),
-                (name + "_avg", double_to_string(s.avg)), (name + "_min", long_to_string(s.min)),
-                (name + "_max", long_to_string(s.max)), (name + "_p50", long_to_string(s.p50)),
-                (name + "_p90", long_to_string(s.p90)), (name + "_p95", long_to_string(s.p95)),
-                (name + "_p99", long_to_string(s.p99)), (name + "_p999", long_to_string(s.p9990)),
-                (name + "_p9999", long_to_string(s.p9999))]
-    return []
+    s = m.snapshotted_summary if kind == N.KIND_STAT else None
+    return [] if s is None else [(name + sfx, text(v)) for (sfx, text), v in zip(_STAT_TEXTS, _stat_values(s))]
 
 
 def write_metrics(tree: MetricsTree, out: List[str], prefix0: Tuple[str, ...] = (), tags0: Tags = ()) -> None:
-    prefix1, tags1 = _rewrite(prefix0, tags0)
-    fields: List[Tuple[str, str]] = []
-    for name, child in tree.children.items():
-        write_metrics(child, out, prefix1 + (name,), tags1)  # deeper lines first (side effect)
-        fields.extend(_fields(name, child.metric))
-    if fields:
-        prefix = prefix1 if prefix1 else ROOT_PREFIX
-        line = escape_key(":".join(prefix))
-        if tags1:
-            line += "," + format_labels(tags1)
-        out.append(line + " " + format_labels(fields) + "\n")
+    for prefix, tags, _, children in walk(tree, prefix0, tags0, post=True):  # deeper lines first
+        fields = [f for name, child in children.items() for f in _fields(name, child.metric)]
+        if fields:
+            line = escape_key(":".join(prefix if prefix else ROOT_PREFIX))
+            if tags:
+                line += "," + format_labels(tags)
+            out.append(line + " " + format_labels(fields) + "\n")
 
 
 class InfluxDbTelemeter:
@@ -111,16 +76,6 @@ class InfluxDbTelemeter:
         id then prints its record; None takes each Stat's snapshotted summary, and a Stat
         without one prints nothing.  A body with an avg outside the device formatter's
         domain is the host writer's text."""
-        import errno
-
-        from ._native import L5dhError
-        from .render_influx import influx_table, render_influx, scrape_inputs
-        if table is None:
-            table = influx_table(self.metrics)
-        table, records, counters, gauges = scrape_inputs(table, summaries)
-        try:
-            return render_influx(engine, table, host, records, counters, gauges)
-        except L5dhError as e:
-            if e.code != -errno.ERANGE:
-                raise
-            return self.render(host).encode("utf-8")
+        inputs = scrape_inputs(influx_table(self.metrics) if table is None else table, summaries)
+        return device_or_host(lambda: render_influx(engine, inputs[0], host, *inputs[1:]),
+                              lambda: self.render(host).encode("utf-8"))

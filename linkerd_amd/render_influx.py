@@ -15,28 +15,24 @@ the table's executable specification.
 from __future__ import annotations
 
 import ctypes
-from typing import List, Tuple
+from typing import List
 
 import numpy as np
 
 from . import _native as N
-from .engine import QUERY, _numel, _record_rows  # noqa: F401  (QUERY: for the callers)
-from .influxdb import ROOT_PREFIX, _rewrite, _utf16_key, escape_key
+from .engine import QUERY, _numel  # noqa: F401  (QUERY: for the callers)
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .prometheus import NO_INDEX
-from .telemetry import Metric, MetricsTree
+from .nametable import (NO_INDEX, escape_key, gather_texts, kind_of, pack_texts, scalar_ordinals,  # noqa: F401
+                        scalar_values, scrape_rows, series_index, uploader, utf16_key, walk)
+from .render_json import value_args
+from .telemetry import MetricsTree
 
-# a Stat's fields in influxdb._fields' order: (key suffix, the field's index in the summary record)
+ROOT_PREFIX = ("root",)
+# a Stat's fields as InfluxDbTelemeter prints them: (key suffix, the field's index in the summary record)
 STAT_FIELDS = (("_count", N.BY_COUNT), ("_sum", N.BY_SUM), ("_avg", N.BY_AVG), ("_min", N.BY_MIN), ("_max", N.BY_MAX),
                ("_p50", N.BY_P50), ("_p90", N.BY_P90), ("_p95", N.BY_P95), ("_p99", N.BY_P99), ("_p999", N.BY_P9990),
                ("_p9999", N.BY_P9999))
-
-
-def _pack(texts):
-    enc = [t.encode("utf-8") for t in texts]
-    off = np.zeros(len(enc) + 1, np.uint64)
-    off[1:] = np.cumsum(np.asarray([len(b) for b in enc], np.uint64))
-    return off, np.frombuffer(b"".join(enc), np.uint8).copy()
+influx_values, _pack = scalar_values, pack_texts  # (the names this module's earlier callers know them by)
 
 
 class InfluxTable:
@@ -79,29 +75,16 @@ class InfluxTable:
         """The table of the given field rows, in that order (a host table); the lines stay
         as they are."""
         rows = np.asarray(rows, np.int64)
-        start = self.key_off[rows].astype(np.int64)
-        length = self.key_off[rows + 1].astype(np.int64) - start
-        key_off = np.zeros(rows.size + 1, np.uint64)
-        key_off[1:] = np.cumsum(length.astype(np.uint64))
-        src = np.repeat(start - key_off[:-1].astype(np.int64), length) + np.arange(int(key_off[-1]), dtype=np.int64)
         metrics = None if self.metrics is None else [self.metrics[int(r)] for r in rows]
         stat_ord = None if self.stat_ord is None else self.stat_ord[rows]
-        return InfluxTable(self.line[rows], self.kinds[rows], self.field[rows], self.index[rows], key_off,
-                           self.key_bytes[src], self.head_off, self.head_bytes, self.tail_off, self.tail_bytes, metrics,
-                           self.stats, stat_ord)
+        return InfluxTable(self.line[rows], self.kinds[rows], self.field[rows], self.index[rows],
+                           *gather_texts(self.key_off, self.key_bytes, rows), self.head_off, self.head_bytes,
+                           self.tail_off, self.tail_bytes, metrics, self.stats, stat_ord)
 
     def to_device(self, device: int = 0) -> "InfluxTable":
         """The same table in device memory (torch tensors): uploaded once, reused by every
         scrape."""
-        import torch
-        dev = torch.device("cuda", int(device))
-
-        def up(a):
-            a = np.ascontiguousarray(a)
-            # (the same bits under torch's long-standing signed types)
-            a = a.view({8: np.int64, 4: np.int32}.get(a.dtype.itemsize, np.uint8)) if a.dtype.kind == "u" else a
-            return torch.from_numpy(a).to(dev)
-        return InfluxTable(*[up(a) for a in self._arrays()[:10]], self.metrics, self.stats, self.stat_ord)
+        return InfluxTable(*map(uploader(device), self._arrays()[:10]), self.metrics, self.stats, self.stat_ord)
 
 
 def influx_table(tree: MetricsTree) -> InfluxTable:
@@ -118,73 +101,56 @@ def influx_table(tree: MetricsTree) -> InfluxTable:
     metrics: list = []
     stat_ord: List[int] = []
     stats: list = []
+    ord_of = {}  # a Stat's place in ``stats``: the walk reaches it before the parent that prints it
     heads: List[str] = []
     tails: List[str] = []
     HOST = ("host", "")  # the request's tag: found again by identity after the sort
     suffixes = [sfx for sfx, _ in STAT_FIELDS]
     stat_kinds, stat_words = [N.KIND_STAT] * 11, [f for _, f in STAT_FIELDS]
 
-    def visit(t: MetricsTree, prefix0: Tuple[str, ...], tags0) -> None:
-        prefix1, tags1 = _rewrite(prefix0, tags0)
+    for prefix, tags, t, children in walk(tree, (), (HOST,), post=True):  # deeper lines first
+        if t is not tree and kind_of(t.metric) == N.KIND_STAT:
+            ord_of[t.metric] = len(stats)
+            stats.append(t.metric)
         # the line's fields in child order, a column each (no object per field: a tree of 10^5 Stats has 10^6)
         ks, kd, fl, ms, so = [], [], [], [], []
-        for name, child in t.children.items():
-            visit(child, prefix1 + (name,), tags1)  # deeper lines first
+        for name, child in children.items():
             m = child.metric
-            if isinstance(m, Metric.Stat):
+            kind = kind_of(m)
+            if kind == N.KIND_STAT:
                 ks += [name + sfx for sfx in suffixes]
                 kd += stat_kinds
                 fl += stat_words
                 ms += [m] * 11
-                so += [len(stats)] * 11
-                stats.append(m)
-            elif isinstance(m, (Metric.Counter, Metric.Gauge)):
+                so += [ord_of[m]] * 11
+            elif kind is not None:
                 ks.append(name)
-                kd.append(N.KIND_COUNTER if isinstance(m, Metric.Counter) else N.KIND_GAUGE)
+                kd.append(kind)
                 fl.append(0)
                 ms.append(m)
                 so.append(0)
         if not ks:
-            return
+            continue
         # the tags split at the host entry itself (tag values are arbitrary text: no placeholder is searched for)
-        tags = sorted(tags1, key=_utf16_key)
+        tags = sorted(tags, key=lambda kv: utf16_key(kv[0]))
         at = next(i for i, kv in enumerate(tags) if kv is HOST)
-        measurement = escape_key(":".join(prefix1 if prefix1 else ROOT_PREFIX))
+        measurement = escape_key(":".join(prefix if prefix else ROOT_PREFIX))
         heads.append(measurement + "".join(f",{k}={v}" for k, v in tags[:at]) + ",host=")
         tails.append("".join(f",{k}={v}" for k, v in tags[at + 1:]) + " ")
         # the stable sort by key, as a permutation (ASCII keys: the code-point order is the UTF-16 order)
         ascii_keys = all(map(str.isascii, ks))
-        order = sorted(range(len(ks)), key=ks.__getitem__ if ascii_keys else lambda i: _utf16_key((ks[i],)))
+        order = sorted(range(len(ks)), key=ks.__getitem__ if ascii_keys else lambda i: utf16_key(ks[i]))
         line.extend([len(heads) - 1] * len(ks))
         for column, values in ((keys, ks), (kinds, kd), (field, fl), (metrics, ms), (stat_ord, so)):
             column.extend([values[i] for i in order])
 
-    visit(tree, (), (HOST,))
     kinds_a = np.asarray(kinds, np.uint8)
     # a stat row's index is its Stat's series id; a counter's or a gauge's its ordinal among the rows of its kind
-    ids = np.asarray([NO_INDEX if m.series_id is None else int(m.series_id) for m in stats] + [NO_INDEX], np.int64)
-    index = ids[np.asarray(stat_ord, np.int64)] if kinds else np.zeros(0, np.int64)
-    for kind in (N.KIND_COUNTER, N.KIND_GAUGE):
-        rows = kinds_a == kind
-        index[rows] = np.arange(int(rows.sum()))
-    key_off, key_bytes = _pack(keys)
-    head_off, head_bytes = _pack(heads)
-    tail_off, tail_bytes = _pack(tails)
-    return InfluxTable(np.asarray(line, np.uint32), kinds_a, np.asarray(field, np.uint8), index.astype(np.uint32), key_off,
-                       key_bytes, head_off, head_bytes, tail_off, tail_bytes, metrics, stats,
+    ids = np.asarray(series_index(stats) + [NO_INDEX], np.int64)
+    index = scalar_ordinals(ids[np.asarray(stat_ord, np.int64)] if kinds else np.zeros(0, np.int64), kinds_a)
+    return InfluxTable(np.asarray(line, np.uint32), kinds_a, np.asarray(field, np.uint8), index.astype(np.uint32),
+                       *pack_texts(keys), *pack_texts(heads), *pack_texts(tails), metrics, stats,
                        np.asarray(stat_ord, np.uint32))
-
-
-def influx_values(table: InfluxTable):
-    """(counters int64, gauges float32) of one scrape: the current values of the counter and
-    gauge rows of a host table, each at the element its row's ``index`` names."""
-    out = []
-    for kind, dtype in ((N.KIND_COUNTER, np.int64), (N.KIND_GAUGE, np.float32)):
-        rows = np.flatnonzero(table.kinds == kind)
-        values = np.zeros(int(table.index[rows].max()) + 1 if rows.size else 0, dtype)
-        values[table.index[rows]] = [table.metrics[int(j)].get() for j in rows]
-        out.append(values)
-    return tuple(out)
 
 
 def scrape_inputs(table: InfluxTable, summaries=None):
@@ -193,23 +159,9 @@ def scrape_inputs(table: InfluxTable, summaries=None):
     -- the rows of a Stat without a series id are dropped; None takes each Stat's
     snapshotted summary, its index its ordinal among the Stats that have one, and drops
     the rows of a Stat without one.  An empty value array is None."""
-    from .prometheus import summary_records
-    stat = table.kinds == N.KIND_STAT
-    counters, gauges = influx_values(table)
-    if summaries is not None:
-        keep = ~stat | (table.index != NO_INDEX)
-    else:
-        snaps = [m.snapshotted_summary for m in table.stats]
-        has = np.asarray([s is not None for s in snaps], bool)
-        shown = [s for s in snaps if s is not None]
-        summaries = summary_records(shown) if shown else None
-        keep = ~stat
-        if has.size:
-            keep = keep | has[table.stat_ord]
-            ordinal = (np.cumsum(has) - 1).astype(np.uint32)
-            table = table.with_index(np.where(stat, ordinal[table.stat_ord], table.index).astype(np.uint32))
-    if not keep.all():
-        table = table.take(np.flatnonzero(keep))
+    counters, gauges = scalar_values(table)
+    stat_of = np.where(table.kinds == N.KIND_STAT, table.stat_ord.astype(np.int64), -1)
+    table, summaries = scrape_rows(table, table.stats, summaries, stat_of)
     return table, summaries, counters if counters.size else None, gauges if gauges.size else None
 
 
@@ -271,14 +223,9 @@ def render_influx(engine, table: InfluxTable, host, summaries, counters, gauges,
     Each value array is host or device memory, or None when no row is of its kind.  Answers
     as render_json does: bytes, or with ``out`` the length written there, or with out=QUERY
     the length alone.  Reads no engine state."""
-    from .render_json import _values
-    sp, ns = None, 0
-    if summaries is not None:
-        sp, ns = engine._records(summaries, N.SUMMARY_DTYPE, "summaries"), _record_rows(summaries, N.SUMMARY_DTYPE)[0]
-    cp, nc = _values(engine, counters, (np.int64,), "counters")
-    gp, ng = _values(engine, gauges, (np.float32,), "gauges")
+    values = value_args(engine, summaries, counters, gauges)
     hb = np.frombuffer(_host_bytes(host), np.uint8)
     nm, n, nl = influx_names(engine, table), table.n, table.nlines
     return engine._render(lambda op, cap, ln: engine._lib.l5dh_render_influx(
-        engine._ctx, ctypes.byref(nm), n, nl, hb.ctypes.data if hb.size else None, _numel(hb), sp, ns, cp, nc, gp, ng,
-        op, cap, ln), "l5dh_render_influx", out)
+        engine._ctx, ctypes.byref(nm), n, nl, hb.ctypes.data if hb.size else None, _numel(hb), *values, op, cap, ln),
+        "l5dh_render_influx", out)

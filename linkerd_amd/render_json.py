@@ -2,7 +2,7 @@
 (l5dh_render_json) and the counter and gauge lines of the Prometheus exposition
 (l5dh_render_scalars), over a HistogramEngine's argument rules.
 
-The tables are prometheus.NameTable with ``kinds`` (uint8 per row: _native.KIND_COUNTER,
+The tables are nametable.NameTable with ``kinds`` (uint8 per row: _native.KIND_COUNTER,
 KIND_GAUGE, KIND_STAT); a row's ``index`` counts within its kind's value array.  Both calls
 answer as HistogramEngine.render_summaries does: bytes, or with ``out`` the length written
 there, or with out=QUERY the length alone.  They read no engine state.
@@ -24,9 +24,15 @@ def _kinds(engine, names):
     return engine._buf(names.kinds, (np.uint8,), "names.kinds", names.n)
 
 
-def _values(engine, x, dtypes, name: str):
-    """(pointer, count) of an optional value array."""
-    return (None, 0) if x is None else (engine._buf(x, dtypes, name), _numel(x))
+def value_args(engine, summaries, counters, gauges):
+    """The six C arguments of a scrape's values: pointer and count of the summary records,
+    the counters (int64) and the gauges (float32), each optional (NULL, 0)."""
+    def values(x, dtype, name):
+        return (None, 0) if x is None else (engine._buf(x, (dtype,), name), _numel(x))
+    sp, ns = None, 0
+    if summaries is not None:
+        sp, ns = engine._records(summaries, N.SUMMARY_DTYPE, "summaries"), _record_rows(summaries, N.SUMMARY_DTYPE)[0]
+    return (sp, ns) + values(counters, np.int64, "counters") + values(gauges, np.float32, "gauges")
 
 
 def render_json(engine, names, summaries, counters, gauges, out=None):
@@ -37,22 +43,17 @@ def render_json(engine, names, summaries, counters, gauges, out=None):
     [n*11]) as ``.count`` and, when count > 0, the nine longs and ``.avg``.  Each value
     array is host or device memory, or None when no row is of its kind.  The table's label
     text is not read.  ``{}`` for a table without rows."""
-    sp, ns = None, 0
-    if summaries is not None:
-        sp, ns = engine._records(summaries, N.SUMMARY_DTYPE, "summaries"), _record_rows(summaries, N.SUMMARY_DTYPE)[0]
-    cp, nc = _values(engine, counters, (np.int64,), "counters")
-    gp, ng = _values(engine, gauges, (np.float32,), "gauges")
+    values = value_args(engine, summaries, counters, gauges)
     nm, n, kp = engine._names(names), names.n, _kinds(engine, names)
     return engine._render(lambda op, cap, ln: engine._lib.l5dh_render_json(
-        engine._ctx, ctypes.byref(nm), kp, n, sp, ns, cp, nc, gp, ng, op, cap, ln), "l5dh_render_json", out)
+        engine._ctx, ctypes.byref(nm), kp, n, *values, op, cap, ln), "l5dh_render_json", out)
 
 
 def render_scalars(engine, names, counters, gauges, out=None):
     """One line ``key[{inner}] <value>`` per row of ``names``, byte for byte
     prometheus.write_scalar_metrics' lines: a counter as a Java long, a gauge as
     Float.toString (never quoted).  A stat row is an error."""
-    cp, nc = _values(engine, counters, (np.int64,), "counters")
-    gp, ng = _values(engine, gauges, (np.float32,), "gauges")
+    values = value_args(engine, None, counters, gauges)[2:]
     nm, n, kp = engine._names(names), names.n, _kinds(engine, names)
     return engine._render(lambda op, cap, ln: engine._lib.l5dh_render_scalars(
-        engine._ctx, ctypes.byref(nm), kp, n, cp, nc, gp, ng, op, cap, ln), "l5dh_render_scalars", out)
+        engine._ctx, ctypes.byref(nm), kp, n, *values, op, cap, ln), "l5dh_render_scalars", out)

@@ -18,10 +18,10 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from ._native import NO_GROUP
-from .javafmt import double_to_string, long_to_string
-from .prometheus import QUANTILES, Labels, _rewrite, escape_key, format_labels
-from .telemetry import HistogramSummary, Metric, MetricsTree, StatEngine
+from ._native import KIND_STAT, NO_GROUP
+from .nametable import Labels, escape_key, kind_of, walk
+from .prometheus import write_rollup_metrics  # noqa: F401  (the groups' lines: a Prometheus writer)
+from .telemetry import HistogramSummary, MetricsTree, StatEngine, live_stats
 
 GroupId = Tuple[str, Labels]
 
@@ -44,23 +44,15 @@ def plan_rollup(tree: MetricsTree, without: Sequence[str], capacity: int) -> Rol
     group_of = np.full(int(capacity), NO_GROUP, dtype=np.uint32)
     index: Dict[GroupId, int] = {}
     groups: List[GroupId] = []
-
-    def visit(t: MetricsTree, prefix0: Tuple[str, ...], labels0: Labels) -> None:
-        prefix1, labels1 = _rewrite(prefix0, labels0)
-        m = t.metric
-        if isinstance(m, Metric.Stat):
-            sid = m.series_id
-            if sid is not None and any(k in drop for k, _ in labels1):
-                gid = (escape_key(":".join(prefix1)), tuple((k, v) for k, v in labels1 if k not in drop))
-                g = index.get(gid)
-                if g is None:
-                    g = index[gid] = len(groups)
-                    groups.append(gid)
-                group_of[sid] = g
-        for name, child in t.children.items():
-            visit(child, prefix1 + (name,), labels1)
-
-    visit(tree, (), ())
+    for prefix, labels, t, _ in walk(tree):
+        sid = t.metric.series_id if kind_of(t.metric) == KIND_STAT else None
+        if sid is not None and any(k in drop for k, _ in labels):
+            gid = (escape_key(":".join(prefix)), tuple((k, v) for k, v in labels if k not in drop))
+            g = index.get(gid)
+            if g is None:
+                g = index[gid] = len(groups)
+                groups.append(gid)
+            group_of[sid] = g
     return RollupPlan(group_of, groups)
 
 
@@ -70,20 +62,6 @@ def snapshot_histograms_rollup(tree: MetricsTree, engine: StatEngine, plan: Roll
     summaries -- of exactly the samples the per-series summaries saw -- are returned."""
     now = time.time()
     series, grouped = engine.snapshot_all_rollup(plan.group_of, max(1, plan.ngroups), reset=True)
-    for _, t in tree.walk():
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            m._set_snapshot(HistogramSummary.from_record(series[m.series_id]), now)
+    for _, m in live_stats(tree):
+        m._set_snapshot(HistogramSummary.from_record(series[m.series_id]), now)
     return [HistogramSummary.from_record(grouped[g]) for g in range(plan.ngroups)]
-
-
-def write_rollup_metrics(plan: RollupPlan, summaries: Sequence[HistogramSummary], out: List[str]) -> None:
-    """Per group the eleven lines a Stat gets from prometheus.write_metrics (_count,
-    _sum, _avg, eight quantiles), with the group's remaining labels."""
-    for (key, labels), s in zip(plan.groups, summaries):
-        lab = format_labels(labels)
-        out.append(f"{key}_count{lab} {long_to_string(s.count)}\n")
-        out.append(f"{key}_sum{lab} {long_to_string(s.sum)}\n")
-        out.append(f"{key}_avg{lab} {double_to_string(s.avg)}\n")
-        for q, field in QUANTILES:
-            out.append(f"{key}{format_labels(labels + (('quantile', q),))} {long_to_string(getattr(s, field))}\n")

@@ -677,17 +677,22 @@ def snapshot_histograms(tree: MetricsTree, engine: StatEngine) -> int:
     return _set_snapshots(tree, engine.snapshot_all)
 
 
+def live_stats(tree: MetricsTree):
+    """(path, Stat) of every Stat of ``tree`` that holds a series id, depth-first."""
+    for path, t in tree.walk():
+        m = t.metric
+        if isinstance(m, Metric.Stat) and m.series_id is not None:
+            yield path, m
+
+
 def _set_snapshots(tree: MetricsTree, snapshot_all) -> int:
     """One resetting snapshot of every series (a StatEngine.snapshot_all*), then each
     Stat's snapshottedSummary and reset time are set from it."""
     now = time.time()
     summaries = snapshot_all(reset=True)
     n = 0
-    for _, t in tree.walk():
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
-            n += 1
+    for n, (_, m) in enumerate(live_stats(tree), 1):
+        m._set_snapshot(HistogramSummary.from_record(summaries[m.series_id]), now)
     return n
 
 
@@ -718,12 +723,7 @@ def window_stats(tree: MetricsTree, engine: StatEngine, last: int, include_open:
     one with ``include_open``), for the Stats of ``tree`` that have a series id.  Nothing is
     reset and no Stat's snapshottedSummary changes.  The reference has no such query."""
     summaries = engine.window_summaries(last, include_open=include_open)
-    out = {}
-    for _, t in tree.walk():
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            out[m] = HistogramSummary.from_record(summaries[m.series_id])
-    return out
+    return {m: HistogramSummary.from_record(summaries[m.series_id]) for _, m in live_stats(tree)}
 
 
 def top_stats(tree: MetricsTree, engine: StatEngine, k: int, by="p99", order: str = "largest", min_count: int = 1,
@@ -738,11 +738,7 @@ def top_stats(tree: MetricsTree, engine: StatEngine, k: int, by="p99", order: st
     to ``tree``'s root, as in flattenMetricsTree."""
     from ._native import NO_GROUP
     scope = tuple(scope)
-    paths = {}
-    for path, t in tree.walk():  # the id -> path map, from one walk
-        m = t.metric
-        if isinstance(m, Metric.Stat) and m.series_id is not None:
-            paths[m.series_id] = path
+    paths = {m.series_id: path for path, m in live_stats(tree)}  # the id -> path map, from one walk
     group = None
     if scope or int(min_count) < 1:  # (min_count = 0 admits empty rows: then only rows that Stats own)
         group = np.full(engine.capacity, NO_GROUP, dtype=np.uint32)

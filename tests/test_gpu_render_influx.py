@@ -11,7 +11,7 @@ import pytest
 from linkerd_amd import _native as N
 from linkerd_amd.influxdb import InfluxDbTelemeter
 from linkerd_amd.prometheus import summary_records
-from linkerd_amd.render_influx import (QUERY, InfluxTable, _pack, influx_names, influx_table, render_host, render_influx,
+from linkerd_amd.render_influx import (QUERY, InfluxTable, pack_texts, influx_names, influx_table, render_host, render_influx,
                                        scrape_inputs)
 from linkerd_amd.telemetry import (HistogramSummary, MetricsTree, MetricsTreeStatsReceiver, StatEngine,
                                    snapshot_histograms)
@@ -122,9 +122,9 @@ def test_output_at_every_skew(eng):
 # ---- the long pieces -------------------------------------------------------------------------
 def crafted(heads, tails, rows):
     """A table from its texts: rows of (line, kind, field, index, key)."""
-    key_off, key_bytes = _pack([r[4] for r in rows])
-    head_off, head_bytes = _pack(heads)
-    tail_off, tail_bytes = _pack(tails)
+    key_off, key_bytes = pack_texts([r[4] for r in rows])
+    head_off, head_bytes = pack_texts(heads)
+    tail_off, tail_bytes = pack_texts(tails)
     col = lambda i, dt: np.asarray([r[i] for r in rows], np.int64).astype(dt)  # noqa: E731
     return InfluxTable(col(0, np.uint32), col(1, np.uint8), col(2, np.uint8), col(3, np.uint32), key_off, key_bytes,
                        head_off, head_bytes, tail_off, tail_bytes)
@@ -248,9 +248,9 @@ def test_contract_sizes(eng):
     assert render_influx(eng, empty, "none", None, None, None, out=QUERY) == 0
     # nlines larger than any used id: more heads and tails than lines with rows
     more = InfluxTable(table.line, table.kinds, table.field, table.index, table.key_off, table.key_bytes,
-                       *_pack([table.head_bytes[int(a):int(b)].tobytes().decode() for a, b in
+                       *pack_texts([table.head_bytes[int(a):int(b)].tobytes().decode() for a, b in
                                zip(table.head_off[:-1], table.head_off[1:])] + ["unused,host="] * 3),
-                       *_pack([table.tail_bytes[int(a):int(b)].tobytes().decode() for a, b in
+                       *pack_texts([table.tail_bytes[int(a):int(b)].tobytes().decode() for a, b in
                                zip(table.tail_off[:-1], table.tail_off[1:])] + [" "] * 3))
     assert more.nlines == table.nlines + 3
     assert render_influx(eng, more, "none", *values) == want

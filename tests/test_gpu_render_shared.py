@@ -12,15 +12,17 @@ import numpy as np
 import pytest
 
 from linkerd_amd import _native as N
-from linkerd_amd.admin_metrics import flat_name_table, scalar_values, write_flat_json
+from linkerd_amd.admin_metrics import AdminMetricsExportTelemeter, flat_name_table, scalar_values, write_flat_json
+from linkerd_amd.influxdb import InfluxDbTelemeter
 from linkerd_amd.javafmt import double_to_string
-from linkerd_amd.prometheus import (scalar_name_table, stat_name_table, summary_records, write_metrics,
-                                    write_quantile_metrics, write_scalar_metrics)
-from linkerd_amd.render_influx import render_influx
+from linkerd_amd.prometheus import (PrometheusTelemeter, line_multiset, scalar_name_table, stat_name_table, summary_records,
+                                    write_metrics, write_quantile_metrics, write_scalar_metrics)
+from linkerd_amd.render_influx import influx_table, render_influx
 from linkerd_amd.render_json import render_json, render_scalars
 from linkerd_amd.telemetry import HistogramSummary, MetricsTree, MetricsTreeStatsReceiver
 
 from . import render_cases as C
+from .influx_cases import rewrite_tree
 from .test_gpu_import import _csr
 from .test_gpu_render import le_case, summary_case
 from .test_gpu_render_influx import contract_case as influx_case
@@ -195,6 +197,54 @@ def test_one_context_all_renderers_in_turn(eng, avgs):
     assert last_error(eng) == "render_influx: the kind of row 12 is none of the three"
     assert eng.render_summaries(stab, svalues) == swant
     assert render_json(eng, jtab, *jvalues) == jwant
+
+
+# ---- every scrape entry point against its host writer, on one small tree ------------------------
+def test_scrape_entry_points_print_the_host_writers_text(eng):
+    """The rewrite cases beside three Stats -- one whole, one without a snapshot, one without
+    a series id: the smallest tree at which a wrong ``index`` or a wrongly kept row shows.
+    Every entry point, table built here and kept, records the Stats' own and given by id."""
+    tree = rewrite_tree()
+    stats = MetricsTreeStatsReceiver(tree)
+    stats.scope("jvm").add_gauge("heap", f=lambda: 1.5)
+    whole = stats.scope("rt", "incoming", "client", "/#/bar").stat("latency_ms")
+    never = stats.scope("foo").stat("never")
+    pruned = stats.stat("pruned")
+    whole.series_id, never.series_id = 3, 1
+    whole._set_snapshot(RECORD)
+    pruned._set_snapshot(HistogramSummary(5, 1, 9, 20, 2, 3, 4, 5, 6, 7, 4.0))
+    prom, admin, influx = PrometheusTelemeter(tree), AdminMetricsExportTelemeter(tree), InfluxDbTelemeter(tree)
+    uri = "/admin/metrics.json"
+
+    def check(summaries, stat_rows):
+        names = stat_name_table(tree)
+        for kept in (None, names, names.to_device()):
+            for on_device in (False, True):
+                got = prom.render_bytes(eng, kept, summaries, scalars_on_device=on_device).decode("utf-8")
+                assert line_multiset(got) == line_multiset(prom.render()) and got.count("_count") == stat_rows
+        for kept in (None, flat_name_table(tree)):
+            status, media, body = admin.handle(uri)
+            assert admin.handle_bytes(uri, eng, kept, summaries) == (status, media, body.encode("utf-8"))
+            assert body.count(".count") == stat_rows
+        for kept in (None, influx_table(tree)):
+            assert influx.render_bytes(eng, "h:80", kept, summaries) == influx.render("h:80").encode("utf-8")
+        assert influx.render("h:80").count("_count=") == stat_rows
+
+    check(None, 2)  # the Stats' own snapshots: `never` prints nothing, `pruned` prints without an id
+    # the snapshot's records by series id: every Stat with an id prints its record, so the host
+    # writers are given the same state -- `never` its record, `pruned` (no id: no record) none
+    recs = np.zeros(8, N.SUMMARY_DTYPE)
+    recs[[3, 1]] = summary_records([RECORD, HistogramSummary(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0)])
+    never._set_snapshot(HistogramSummary.from_record(recs[1]))
+    pruned._set_snapshot(None)
+    for kept in (None, flat_name_table(tree)):
+        status, media, body = admin.handle(uri)
+        assert admin.handle_bytes(uri, eng, kept, recs) == (status, media, body.encode("utf-8"))
+    for kept in (None, influx_table(tree)):
+        assert influx.render_bytes(eng, "h:80", kept, _dev(recs.view(np.int64))) == influx.render("h:80").encode("utf-8")
+    # (the Prometheus table takes no row without an id when the records go by id: the Stat is gone)
+    stats.prune("pruned")
+    check(recs, 2)
 
 
 # ---- the sparse export and the window push beside a render call --------------------------------

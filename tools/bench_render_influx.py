@@ -45,7 +45,7 @@ def stat_fields_table(S):
     import numpy as np
 
     from linkerd_amd import _native as N
-    from linkerd_amd.render_influx import STAT_FIELDS, InfluxTable, _pack
+    from linkerd_amd.render_influx import STAT_FIELDS, InfluxTable, pack_texts
     fields = sorted(STAT_FIELDS)  # (ASCII suffixes: the UTF-16 order)
     keys = [(STAT + sfx).encode() for sfx, _ in fields]
     klen = np.asarray([len(k) for k in keys], np.uint64)
@@ -53,8 +53,8 @@ def stat_fields_table(S):
     key_off[1:] = np.cumsum(np.tile(klen, S))
     key_bytes = np.tile(np.frombuffer(b"".join(keys), np.uint8), S)
     sc = [scope_of(j) for j in range(S)]
-    head_off, head_bytes = _pack([f"rt:client,client={s[3]},host=" for s in sc])
-    tail_off, tail_bytes = _pack([f",rt={s[1]} " for s in sc])
+    head_off, head_bytes = pack_texts([f"rt:client,client={s[3]},host=" for s in sc])
+    tail_off, tail_bytes = pack_texts([f",rt={s[1]} " for s in sc])
     series = np.repeat(np.arange(S, dtype=np.uint32), 11)
     return InfluxTable(series.copy(), np.full(11 * S, N.KIND_STAT, np.uint8),
                        np.tile(np.asarray([f for _, f in fields], np.uint8), S), series, key_off, key_bytes, head_off,
