@@ -524,16 +524,39 @@ struct Bin1Half {
   float f[B1_PH];
 };
 
-// Issues the loads of half `h` of the full sub-chunk at c0.
-__device__ __forceinline__ Bin1Regs b1_issue_half(const uint32_t* series, const float* values, uint32_t c0, int h) {
+// Issues the loads of half `h` of the full sub-chunk at c0 -- under no branch: where there is
+// no such sub-chunk (`ok` false) every lane re-reads the 16 bytes at `spare` and nothing uses
+// the registers.  On gfx9 loads, returning atomics and stores share one in-order counter, and
+// the compiler counts the operations younger than the one it waits for only where they are
+// issued unconditionally.  Issued under `if (ok)`, these loads made every later wait of the
+// sub-chunk s_waitcnt vmcnt(0), and the registers they fill were copied, behind such a wait,
+// right where the loads were issued (profiles/level1_waits_ab.txt has the ISA).
+__device__ __forceinline__ Bin1Regs b1_issue_half(const uint32_t* series, const float* values, uint32_t c0, int h,
+                                                  bool ok, const uint32_t* spare) {
   Bin1Regs r;
 #pragma unroll
   for (int k = 0; k < B1_HG; ++k) {
     const uint32_t base = b1_slot(c0, h * B1_HG + k, 0);
-    r.s[k] = ld_stream(series + base);
-    r.v[k] = ld_stream(reinterpret_cast<const uint32_t*>(values) + base);
+    r.s[k] = ld_stream(ok ? series + base : spare);
+    r.v[k] = ld_stream(ok ? reinterpret_cast<const uint32_t*>(values) + base : spare);
   }
   return r;
+}
+// Wait points by structure, not by wait immediates: an empty statement that takes loaded
+// registers as operands has the compiler wait for them here, where nothing younger is
+// outstanding, and leaves no later use of them to wait behind whatever was issued since.
+static_assert(B1_HG == 2 && B1_PH == 8, "the arrive points name a half's 16 registers");
+__device__ __forceinline__ void b1_arrive(Bin1Regs& r) {
+  asm volatile(""
+               : "+v"(r.s[0].x), "+v"(r.s[0].y), "+v"(r.s[0].z), "+v"(r.s[0].w), "+v"(r.s[1].x), "+v"(r.s[1].y),
+                 "+v"(r.s[1].z), "+v"(r.s[1].w), "+v"(r.v[0].x), "+v"(r.v[0].y), "+v"(r.v[0].z), "+v"(r.v[0].w),
+                 "+v"(r.v[1].x), "+v"(r.v[1].y), "+v"(r.v[1].z), "+v"(r.v[1].w));
+}
+__device__ __forceinline__ void b1_arrive(Bin1Half& x) {
+  asm volatile(""
+               : "+v"(x.s[0]), "+v"(x.s[1]), "+v"(x.s[2]), "+v"(x.s[3]), "+v"(x.s[4]), "+v"(x.s[5]), "+v"(x.s[6]),
+                 "+v"(x.s[7]), "+v"(x.f[0]), "+v"(x.f[1]), "+v"(x.f[2]), "+v"(x.f[3]), "+v"(x.f[4]), "+v"(x.f[5]),
+                 "+v"(x.f[6]), "+v"(x.f[7]));
 }
 
 // A half's samples from the registers b1_issue_half filled (a full sub-chunk) ...
@@ -627,8 +650,13 @@ __device__ __forceinline__ uint4 b1_rank_group(uint32_t* smem, int h, int g, Bin
     for (int q = 0; q < GS; ++q) {
       if ((escm >> q) & 1u) {
         const uint32_t i = b1_slot(c0, h * B1_HG + (g + q) / 4, q & 3);
-        const uint32_t si = series[i];
-        const uint32_t r = payload1_slow(si, values[i], tb, pass == 0 ? sumfix : nullptr);
+        // (both re-reads arrive here: a path through the search that never used the value left
+        // its load pending, and the join after this loop then waited, on every group of every
+        // sub-chunk, for everything outstanding -- the write-out's stores, the second half's loads)
+        uint32_t si = series[i];
+        float vi = values[i];
+        asm volatile("" : "+v"(si), "+v"(vi));
+        const uint32_t r = payload1_slow(si, vi, tb, pass == 0 ? sumfix : nullptr);
         if (pass == 0 && r - DSUM_PMAX < V_ESC - DSUM_PMAX) {
           // not escaped, but too large for a u32 sum: a direct series' value goes to sumfix here
           const uint2 d = dw[(si >> (TILE_SHIFT + 5)) & 1023u];
@@ -868,9 +896,11 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
     breg[b] = b < TB ? make_uint2(bbase[b], bcap[b]) : make_uint2(0u, 0u);
   }
   PH_INIT
-  // the next sub-chunk's first half, loaded during this one's scatter / write-out
-  Bin1Regs pf;
-  if (vec && lo + (uint32_t)CHW <= hi) pf = b1_issue_half(series, values, lo, 0);
+  // the next sub-chunk's first half, loaded while this one's last group is ranked and arrived
+  // before this one's write-out; a load that has no sub-chunk to read re-reads a table's start
+  const uint32_t* const spare = reinterpret_cast<const uint32_t*>(tb.lim_pad);
+  Bin1Regs pf = b1_issue_half(series, values, lo, 0, vec && lo + (uint32_t)CHW <= hi, spare);
+  b1_arrive(pf);
   for (uint32_t c0 = lo; c0 < hi; c0 += CHW) {
     for (uint32_t wd = threadIdx.x; wd < CHW / 32; wd += NT1) heads[wd] = 0u;
     // records are staged in slot order first (the stage is free until the scatter), so
@@ -886,6 +916,7 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
         hf = b1_unpack_half(h == 0 ? pf : sh);
       } else {
         hf = b1_load_ragged(series, values, c0, hi, h);
+        b1_arrive(hf);  // (in this branch: pending at the join, they made the full path wait as well)
         bad |= b1_ragged_invalid(hf, c0, hi, h, S);
       }
       if (full) {  // (phase stamps: the half's loads -- and, on gfx9, every older store -- done)
@@ -897,7 +928,15 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
         // the second half, issued once the first half's first group is ranked (in flight through
         // the rest of its ranking): bin1 3.25-3.30 -> 3.18 ms on C3 (issued before the first group,
         // or at the second half's start as in round 4, 3.36 / 3.25; profiles/r05w_second_half_ab.txt)
-        if (h == 0 && g == B1_GS && full) sh = b1_issue_half(series, values, c0, 1);
+        if (h == 0 && g == B1_GS) sh = b1_issue_half(series, values, c0, 1, full, spare);
+        // the next sub-chunk's first half, before the last group: in flight through that group, the
+        // wait at B1 and the phases up to B3 (≈ 5 us), with no store behind it.  It is older than
+        // the run reservations' atomics, so the run deltas' wait for those covers nothing younger;
+        // b1_arrive below finds it done.  (Issued after B2, as before, a load had 1.9 us to B3 and
+        // the arrive point cost 0.05 ms; after B1 it delayed the reservations: +0.09 ms; before B1
+        // or before the second half's first group -0.04 ms, here -0.09: profiles/level1_waits_ab.txt)
+        if (h == 1 && g == B1_PH - B1_GS)
+          pf = b1_issue_half(series, values, c0 + (uint32_t)CHW, 0, vec && c0 + 2u * (uint32_t)CHW <= hi, spare);
         b1_progress_prio(h * (B1_PH / B1_GS) + g / B1_GS);
         if (full) bad |= b1_group_invalid(hf, g, S);
         const uint4 p4 = b1_rank_group(smem, h, g, hf, series, values, c0, S, FS, TB, tb, sumfix, pass);
@@ -921,8 +960,6 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
     b1_read_slots(smem, rec);
     __syncthreads();  // B2: offsets, run ranks, heads; every slot-order record read
     PH_MARK(4)
-    // (after B2: the run reservations' returns and the scan never wait behind these loads)
-    if (vec && c0 + 2u * (uint32_t)CHW <= hi) pf = b1_issue_half(series, values, c0 + (uint32_t)CHW, 0);
 #pragma unroll
     for (int k = 0; k < B1_PT; ++k) b1_scatter(smem, pk[k], rec[k]);
     if (wv == 0) b1_group_prefixes(smem, lane);
@@ -931,6 +968,10 @@ __global__ __launch_bounds__(NT1) void k_rbin1w(const uint32_t* __restrict__ ser
     PH_MARK(5)
     const uint32_t nst = offr_run(offr[FS]);  // runs of super-tile bins
     cnt[threadIdx.x] = 0;
+    // the next first half's wait point: nothing is outstanding but those loads (the run deltas
+    // waited for them already), so the next sub-chunk's ranking starts without a wait and the
+    // write-out's stores are never waited for
+    b1_arrive(pf);
     b1_write_out(smem, wv, lane, nst, rec32, rec16);
     __syncthreads();  // B4
     PH_MARK(6)
