@@ -82,7 +82,8 @@ enum {
                                   every variant computes the same results; bit 0: one-tile folds in u16 bins;
                                   bit 1: DMA copies of pinned host batches; bit 2: every ingest batch's
                                   capacity plan made as for a first interval, from its sample alone;
-                                  other bits are ignored) */
+                                  bit 3: l5dh_counters_add without the LDS claim table, one global atomic
+                                  per add; other bits are ignored) */
 };
 
 /* Fleet-merge modes for l5dh_merge */
@@ -103,7 +104,8 @@ enum {
   L5DH_K_BIN2 = 6,   /* level-2 partition (super-tile regions -> 16-bit per-key records, + its redo) */
   L5DH_K_MERGE = 7,  /* the RCCL collective of l5dh_merge */
   L5DH_K_WINDOW = 8, /* the sliding window's sum over its slots (l5dh_window_query) */
-  L5DH_K_NKERNELS = 9
+  L5DH_K_COUNTERS = 9, /* the counter space's batched add and rollup (l5dh_counters_add, l5dh_counters_rollup) */
+  L5DH_K_NKERNELS = 10
 };
 
 /* Reference: BucketedHistogram() per Stat (MetricsTree.scala:88).  Opens a
@@ -446,6 +448,65 @@ int l5dh_window_forget(l5dh_ctx* ctx, uint32_t first, uint32_t count);
 int l5dh_window_move(l5dh_ctx* from, l5dh_ctx* to);
 int l5dh_window_info(l5dh_ctx* ctx, uint32_t* slots, uint32_t* filled, uint64_t* pushes, uint64_t* entries,
                      uint64_t* bytes);
+
+/* Counters on the device: Metric.Counter (Metric.scala:14-20, an AtomicLong behind
+ * incr(delta: Int)), batched.  A context may own a counter space: int64 values
+ * [max_counters] in device memory, all zero when opened; nothing is allocated before.  Every
+ * sum is a two's-complement sum that wraps like a Java long, so the order of adds never
+ * shows.  Every data pointer may be host or device memory (at any 4-byte alignment for ids,
+ * deltas and the group map, 8-byte for the values); every call holds the context's lock.
+ * Arguments are checked on the host before anything is enqueued, and a failing call changes
+ * nothing: -EINVAL for a null context, a context without counters, a range outside the
+ * space, max_counters outside [1, L5DH_MAX_COUNTERS], ngroups outside [1,
+ * L5DH_MAX_COUNTERS], n above 2^30.
+ *
+ * l5dh_counters_open: -EEXIST if the context already has counters.  l5dh_counters_close
+ * frees the space; l5dh_close frees it too.  l5dh_counters_resize grows only (a smaller size
+ * is -EINVAL): the values are kept and the new ones are 0.
+ *
+ * l5dh_counters_add: values[ids[i]] += deltas[i] for i < n (deltas == NULL: 1 each).  It
+ * follows l5dh_ingest's contract: it returns once the batch is queued, host buffers are free
+ * again when it returns, device buffers are stream ordered on a caller stream
+ * (l5dh_set_stream) and free when it returns otherwise.  An id >= max_counters is dropped --
+ * never applied, never an address -- and counted: the next l5dh_sync returns -EINVAL (once)
+ * for them, and l5dh_counters_info's *dropped holds their number.  Every valid add is
+ * applied.
+ *
+ * l5dh_counters_read / l5dh_counters_write: values [first, first + count) to out / from
+ * values (NULL: zeros), ordered with the adds queued before.  count == 0 does nothing.
+ *
+ * l5dh_counters_rollup: label rollups of counters ("requests per router"): g_out[g] for g <
+ * ngroups receives the wrapping sum of the counters first + i, i < count, with group[i] == g
+ * -- l5dh_rollup's map: a value < ngroups or L5DH_NO_GROUP.  Any other value is -EINVAL,
+ * found on the device and reported by this call, l5dh_last_error naming the least such index;
+ * that entry counts as no group.  A group without members gives 0; count == 0 still writes
+ * ngroups zeros.
+ *
+ * l5dh_counters_values: the live array, for a renderer on the same context and stream
+ * (l5dh_render_json, l5dh_render_scalars, l5dh_render_influx take it as `counters`), so a
+ * scrape copies nothing.  Valid until the next resize, move or close.
+ *
+ * l5dh_counters_move hands the space of `from` to `to`, a context on the same device that
+ * has none (-EEXIST): the pointer moves, nothing is copied.  The two locks are taken in
+ * address order.
+ *
+ * l5dh_counters_info (every pointer nullable): the space's size and what the add kernels
+ * counted since it was opened: *adds the adds applied, of which *lds_adds went through a
+ * workgroup's LDS claim table and *global_adds took a global atomic of their own (*adds ==
+ * *lds_adds + *global_adds), and *dropped the invalid ids. */
+#define L5DH_MAX_COUNTERS (1u << 24)
+int l5dh_counters_open(l5dh_ctx* ctx, uint32_t max_counters);
+int l5dh_counters_close(l5dh_ctx* ctx);
+int l5dh_counters_resize(l5dh_ctx* ctx, uint32_t max_counters);
+int l5dh_counters_add(l5dh_ctx* ctx, const uint32_t* ids, const int32_t* deltas /* nullable: 1 */, size_t n);
+int l5dh_counters_read(l5dh_ctx* ctx, uint32_t first, uint32_t count, int64_t* out);
+int l5dh_counters_write(l5dh_ctx* ctx, uint32_t first, uint32_t count, const int64_t* values /* nullable: 0 */);
+int l5dh_counters_rollup(l5dh_ctx* ctx, uint32_t first, uint32_t count, const uint32_t* group, uint32_t ngroups,
+                         int64_t* g_out);
+int l5dh_counters_values(l5dh_ctx* ctx, const int64_t** device_ptr, uint32_t* max_counters);
+int l5dh_counters_move(l5dh_ctx* from, l5dh_ctx* to);
+int l5dh_counters_info(l5dh_ctx* ctx, uint32_t* max_counters, uint64_t* adds, uint64_t* lds_adds,
+                       uint64_t* global_adds, uint64_t* dropped);
 
 /* Java number texts, as the exporters print them (host only, no context): Long.toString,
  * the unsigned 64-bit decimal (the `le` counts) and Double.toString as JDK 8 prints it

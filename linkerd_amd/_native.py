@@ -45,6 +45,8 @@ MAX_SERIES = 1 << 20  # L5DH_MAX_SERIES
 LE_MAX = 64  # L5DH_LE_MAX
 Q_MAX = 64  # L5DH_Q_MAX
 WINDOW_MAX = 64  # L5DH_WINDOW_MAX: slots of a sliding window
+MAX_COUNTERS = 1 << 24  # L5DH_MAX_COUNTERS: counters of a context's counter space
+VARIANT_COUNTERS_PLAIN = 8  # L5DH_PARAM_VARIANT bit 3: counters_add without the LDS claim table
 DOUBLE_CHARS = 26  # L5DH_DOUBLE_CHARS
 FLOAT_CHARS = 16  # L5DH_FLOAT_CHARS
 KIND_COUNTER, KIND_GAUGE, KIND_STAT = 0, 1, 2  # L5DH_KIND_*: a row's kind in render_json / render_scalars
@@ -76,8 +78,8 @@ MERGE_ALL_REDUCE = 1
 UNIQUE_ID_BYTES = 128
 OWN_STREAM = ctypes.c_void_p(-1 & (2 ** 64 - 1)).value  # L5DH_OWN_STREAM
 
-K_COUNT, K_SCAN, K_BIN, K_ACCUM, K_HOT, K_COPY, K_BIN2, K_MERGE, K_WINDOW = range(9)
-KERNEL_NAMES = ("count", "scan", "bin1", "accum", "hot", "copy", "bin2", "merge", "window")
+K_COUNT, K_SCAN, K_BIN, K_ACCUM, K_HOT, K_COPY, K_BIN2, K_MERGE, K_WINDOW, K_COUNTERS = range(10)
+KERNEL_NAMES = ("count", "scan", "bin1", "accum", "hot", "copy", "bin2", "merge", "window", "counters")
 
 
 class NativeLibraryMissing(ImportError):
@@ -131,6 +133,17 @@ SIGNATURES = {
     "l5dh_window_move": (_c.c_int, [_vp, _vp]),
     "l5dh_window_info": (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64),
                                     _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "l5dh_counters_open": (_c.c_int, [_vp, _c.c_uint32]),
+    "l5dh_counters_close": (_c.c_int, [_vp]),
+    "l5dh_counters_resize": (_c.c_int, [_vp, _c.c_uint32]),
+    "l5dh_counters_add": (_c.c_int, [_vp, _vp, _vp, _c.c_size_t]),
+    "l5dh_counters_read": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp]),
+    "l5dh_counters_write": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp]),
+    "l5dh_counters_rollup": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _c.c_uint32, _vp]),
+    "l5dh_counters_values": (_c.c_int, [_vp, _c.POINTER(_vp), _c.POINTER(_c.c_uint32)]),
+    "l5dh_counters_move": (_c.c_int, [_vp, _vp]),
+    "l5dh_counters_info": (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                      _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     "l5dh_format_double": (_c.c_int, [_c.c_double, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_float": (_c.c_int, [_c.c_float, _vp, _c.POINTER(_c.c_size_t)]),
     "l5dh_format_long": (_c.c_int, [_c.c_int64, _vp, _c.POINTER(_c.c_size_t)]),

@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _native as N
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .nametable import (NO_INDEX, NameTable, device_or_host, kind_of, scalar_ordinals, scalar_values,  # noqa: F401
-                        scrape_rows, series_index, utf16_key)
+from .nametable import (NO_INDEX, NameTable, bulk_counters, counter_ids, device_or_host, kind_of, nonempty,  # noqa: F401
+                        scalar_ordinals, scalar_values, scrape_rows, series_index, utf16_key)
 from .render_json import render_json
 from .telemetry import Metric, MetricsTree, StatEngine, snapshot_histograms
 
@@ -146,7 +146,7 @@ def flat_name_table(tree: MetricsTree) -> NameTable:
     flatten_metrics_tree order, its key the ``a/b/c`` name escaped as json_string escapes
     it (without the quotes), no label text.  A stat's ``index`` is its series id (NO_INDEX
     without one); a counter's or a gauge's is its ordinal among the rows of its kind, the
-    order of scalar_values."""
+    order of scalar_values -- or, for a counter that lives in a CounterEngine, its counter id."""
     keys, metrics, kinds = [], [], []
     for name, m in flatten_metrics_tree(tree):
         kind = kind_of(m)
@@ -157,7 +157,8 @@ def flat_name_table(tree: MetricsTree) -> NameTable:
     kinds = np.asarray(kinds, np.uint8)
     index = np.full(kinds.size, NO_INDEX, np.int64)
     index[kinds == N.KIND_STAT] = series_index(m for m, kind in zip(metrics, kinds) if kind == N.KIND_STAT)
-    return NameTable.build(keys, [""] * len(keys), scalar_ordinals(index, kinds), metrics, kinds)
+    return NameTable.build(keys, [""] * len(keys), counter_ids(scalar_ordinals(index, kinds), kinds, metrics),
+                           metrics, kinds)
 
 
 def _write_tree(jg: _Gen, tree: MetricsTree) -> None:
@@ -226,7 +227,8 @@ class AdminMetricsExportTelemeter:
         sub = self.metrics.try_resolve(_java_split_slash(q)) if q is not None else self.metrics
         if sub is None:
             return 404, "application/json", '{"error": "No such subtree: %s"}' % q
-        body = write_json_tree(sub) if tree else write_flat_json(sub, pretty)
+        with bulk_counters(self.metrics):
+            body = write_json_tree(sub) if tree else write_flat_json(sub, pretty)
         return 200, "application/json", body
 
     def handle_bytes(self, uri: str, engine, names=None, summaries=None) -> Tuple[int, str, bytes]:
@@ -250,9 +252,11 @@ class AdminMetricsExportTelemeter:
         # the kept Stats' records beside them, in table order (summaries None), or the snapshot's by series id
         table, records = scrape_rows(table, [m for m, is_stat in zip(table.metrics, stat) if is_stat], summaries,
                                      np.where(stat, np.cumsum(stat) - 1, -1))
-        body = device_or_host(lambda: render_json(engine, table, records, counters if counters.size else None,
-                                                  gauges if gauges.size else None),
-                              lambda: write_flat_json(sub, False).encode("utf-8"))
+        def host_writer():
+            with bulk_counters(self.metrics):
+                return write_flat_json(sub, False).encode("utf-8")
+        body = device_or_host(lambda: render_json(engine, table, records, nonempty(counters), nonempty(gauges)),
+                              host_writer)
         return 200, "application/json", body
 
     # -- snapshot driver -----------------------------------------------------

@@ -1,5 +1,5 @@
 // l5dh_ctx.hpp -- private to the host side (l5dh_engine.cpp, l5dh_queries.cpp,
-// l5dh_fleet.cpp, l5dh_window_host.cpp): the context behind the C-ABI's opaque l5dh_ctx, the owner of its
+// l5dh_fleet.cpp, l5dh_window_host.cpp, l5dh_counters_host.cpp): the context behind the C-ABI's opaque l5dh_ctx, the owner of its
 // device memory, and the helpers the files share (defined in l5dh_engine.cpp).
 #pragma once
 
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/l5dhist.h"
+#include "l5dh_counters.hpp"
 #include "l5dh_import.hpp"
 #include "l5dh_influx.hpp"
 #include "l5dh_kernels.hpp"
@@ -182,6 +183,15 @@ struct l5dh_ctx {
     uint32_t born_n = 0;
   };
   std::unique_ptr<Window> win;  // (freed after ~l5dh_ctx has drained the stream, as every device buffer)
+  // the counter space (l5dh_counters_host.cpp): values [max] int64, the kernels' statistics words
+  // (stats [CS_WORDS] u64), the rollup's status word, the staged inputs of an add and of a rollup
+  struct Counters {
+    DevBuf values, stats, status;
+    uint32_t max = 0;
+    uint64_t dropped_reported = 0;  // dropped ids already returned by l5dh_sync
+    DevBuf stage_ids, stage_deltas, stage_vals, stage_group, stage_out;
+  };
+  std::unique_ptr<Counters> cnt;
   uint32_t rollup_item = l5dh::RU_ITEM_DEFAULT;  // members per work item (L5DH_PARAM_ROLLUP_ITEM)
   uint32_t variant = 0;  // L5DH_PARAM_VARIANT: result-preserving kernel variants (A/B timing)
   // params
@@ -300,6 +310,9 @@ int live_begin(l5dh_ctx* c);
 int rows_of_range(l5dh_ctx* c, uint32_t first, uint32_t count, Summary88* summ_dev, int reset);
 // -EINVAL unless [first, first + count) lies within the series space.
 int check_range(l5dh_ctx* c, uint32_t first, uint32_t count);
+// l5dh_sync's share of the counter space (l5dh_counters_host.cpp), after the stream has been
+// drained: -EINVAL once for ids dropped since the last such report.
+int counters_check(l5dh_ctx* c);
 
 // n elements of a small host or device array to the host: one copy, and one wait if it
 // was device memory.

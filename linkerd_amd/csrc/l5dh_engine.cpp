@@ -708,7 +708,8 @@ int l5dh_sync(l5dh_ctx* c) {
   CtxLock g(c);
   int r;
   if ((r = flush_ring(c)) || (r = sync_stream(c))) return r;
-  return check_err(c);
+  if ((r = check_err(c))) return r;
+  return c->cnt ? counters_check(c) : 0;
 }
 
 int l5dh_set_stream(l5dh_ctx* c, void* s) {

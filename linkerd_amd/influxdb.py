@@ -20,7 +20,7 @@ from typing import List, Sequence, Tuple
 
 from . import _native as N
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .nametable import device_or_host, escape_key, kind_of, utf16_key, walk  # noqa: F401
+from .nametable import bulk_counters, device_or_host, escape_key, kind_of, utf16_key, walk  # noqa: F401
 from .render_influx import ROOT_PREFIX, STAT_FIELDS, influx_table, render_influx, scrape_inputs
 from .telemetry import MetricsTree
 
@@ -65,7 +65,8 @@ class InfluxDbTelemeter:
     def render(self, host: str = "none") -> str:
         """The handler body; `host` is the request's Host header ("none" if absent)."""
         out: List[str] = []
-        write_metrics(self.metrics, out, (), (("host", host),))
+        with bulk_counters(self.metrics):
+            write_metrics(self.metrics, out, (), (("host", host),))
         return "".join(out)
 
     def render_bytes(self, engine, host: str = "none", table=None, summaries=None) -> bytes:

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import errno
 import re
+from contextlib import nullcontext
 from typing import Iterator, Sequence, Tuple
 
 import numpy as np
@@ -75,12 +76,32 @@ def kind_of(metric):
     return _KIND_OF.get(type(metric))
 
 
+def counter_engine(metrics):
+    """The counters.CounterEngine behind the device-backed counters among ``metrics`` (those
+    of one tree share one), None when the counters are host values."""
+    for m in metrics:
+        if type(m) is Metric.Counter:
+            return m._counters
+    return None
+
+
 def scalar_ordinals(index: np.ndarray, kinds: np.ndarray) -> np.ndarray:
     """``index`` with every counter and gauge row's entry set to its ordinal among the rows
     of its kind: the element of scalar_values' array it prints."""
     for kind in (N.KIND_COUNTER, N.KIND_GAUGE):
         rows = kinds == kind
         index[rows] = np.arange(int(rows.sum()))
+    return index
+
+
+def counter_ids(index: np.ndarray, kinds: np.ndarray, metrics) -> np.ndarray:
+    """``index`` (scalar_ordinals') of the rows of ``metrics``: when the counters live in a
+    CounterEngine, a counter row's entry becomes its counter id (NO_INDEX once pruned), the
+    element of the engine's live array it prints; unchanged for host counters."""
+    if counter_engine(metrics) is not None:
+        rows = kinds == N.KIND_COUNTER
+        index[rows] = [NO_INDEX if m.counter_id is None else m.counter_id
+                       for m, is_counter in zip(metrics, rows) if is_counter]
     return index
 
 
@@ -92,14 +113,33 @@ def series_index(stats) -> list:
 def scalar_values(table):
     """(counters int64, gauges float32) of one scrape: the current values of the counter and
     gauge rows of a host table (NameTable with kinds, InfluxTable), each at the element its
-    row's ``index`` names."""
+    row's ``index`` names.  Counters that live in a CounterEngine are not read: the counters
+    are then its live device array (CounterEngine.device_values, a torch tensor), which the
+    rows index by counter id -- for a renderer on the CounterEngine's own engine."""
     out = []
     for kind, dtype in ((N.KIND_COUNTER, np.int64), (N.KIND_GAUGE, np.float32)):
         rows = np.flatnonzero(table.kinds == kind)
+        ce = counter_engine(table.metrics[int(j)] for j in rows[:1]) if kind == N.KIND_COUNTER else None
+        if ce is not None:
+            out.append(ce.device_values())
+            continue
         values = np.zeros(int(table.index[rows].max()) + 1 if rows.size else 0, dtype)
         values[table.index[rows]] = [table.metrics[int(j)].get() for j in rows]
         out.append(values)
     return tuple(out)
+
+
+def nonempty(values):
+    """A value array of scalar_values, or None when it holds nothing (the renderers' NULL)."""
+    return values if (values.size if isinstance(values, np.ndarray) else values.numel()) else None
+
+
+def bulk_counters(tree: MetricsTree):
+    """The block in which a host writer prints ``tree``: with a CounterEngine behind the
+    tree's counters, one bulk read of its values answers every counter's get() inside (no
+    device read per counter); without one, nothing changes."""
+    ce = getattr(tree, "_counters", None)
+    return nullcontext() if ce is None else ce.bulk_reads()
 
 
 # ---- table plumbing --------------------------------------------------------------------------

@@ -19,8 +19,8 @@ import numpy as np
 
 from . import _native as N
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .nametable import (NO_INDEX, Labels, NameTable, escape_key, kind_of, scalar_ordinals, scalar_values,  # noqa: F401
-                        scrape_rows, series_index, summary_records, walk)
+from .nametable import (NO_INDEX, Labels, NameTable, bulk_counters, counter_ids, escape_key, kind_of,  # noqa: F401
+                        scalar_ordinals, scalar_values, scrape_rows, series_index, summary_records, walk)
 from .render_json import render_scalars
 from .telemetry import MetricsTree
 
@@ -159,10 +159,12 @@ def stat_name_table(tree: MetricsTree) -> NameTable:
 def scalar_name_table(tree: MetricsTree) -> NameTable:
     """The name table of the counters and gauges of ``tree``: one row per counter or gauge
     in write_scalar_metrics' order with its kind, ``index`` its ordinal among the rows of
-    its kind (the order of scalar_values)."""
+    its kind (the order of scalar_values) -- or, for a counter that lives in a CounterEngine,
+    its counter id."""
     keys, inners, metrics = _name_rows(tree, (N.KIND_COUNTER, N.KIND_GAUGE))
     kinds = np.asarray([kind_of(m) for m in metrics], np.uint8)
-    return NameTable.build(keys, inners, scalar_ordinals(np.zeros(kinds.size, np.int64), kinds), metrics, kinds)
+    return NameTable.build(keys, inners, counter_ids(scalar_ordinals(np.zeros(kinds.size, np.int64), kinds), kinds, metrics),
+                           metrics, kinds)
 
 
 def rollup_name_table(plan) -> NameTable:
@@ -190,8 +192,9 @@ class PrometheusTelemeter:
     def render(self) -> str:
         out: List[str] = []
         nodes = list(walk(self.metrics))  # one walk: every block describes the same Stats
-        for node in nodes:
-            _metric_lines(*node, out)
+        with bulk_counters(self.metrics):
+            for node in nodes:
+                _metric_lines(*node, out)
         if self.rollups is not None:
             write_rollup_metrics(*self.rollups, out)
         if self.histograms is not None:
@@ -220,7 +223,8 @@ class PrometheusTelemeter:
             parts = [render_scalars(engine, scalars, *scalar_values(scalars)) if scalars.n else b""]
         else:
             out: List[str] = []
-            write_scalar_metrics(self.metrics, out)
+            with bulk_counters(self.metrics):
+                write_scalar_metrics(self.metrics, out)
             parts = ["".join(out).encode("utf-8")]
         table = stat_name_table(self.metrics) if names is None else names
         host = table if table.metrics is not None and isinstance(table.key_off, np.ndarray) else None

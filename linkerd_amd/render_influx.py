@@ -22,7 +22,7 @@ import numpy as np
 from . import _native as N
 from .engine import QUERY, _numel  # noqa: F401  (QUERY: for the callers)
 from .javafmt import double_to_string, float_to_string, long_to_string
-from .nametable import (NO_INDEX, escape_key, gather_texts, kind_of, pack_texts, scalar_ordinals,  # noqa: F401
+from .nametable import (NO_INDEX, counter_ids, escape_key, gather_texts, kind_of, nonempty, pack_texts, scalar_ordinals,  # noqa: F401
                         scalar_values, scrape_rows, series_index, uploader, utf16_key, walk)
 from .render_json import value_args
 from .telemetry import MetricsTree
@@ -93,7 +93,8 @@ def influx_table(tree: MetricsTree) -> InfluxTable:
     first), the same prefix rewrite, escape and ``root`` prefix, the same stable sorts by
     UTF-16 code units over a line's fields in child order and over its tags.  Every Stat has
     its eleven rows, snapshot or not; a stat row's ``index`` is the series id (NO_INDEX
-    without one), a counter's or gauge's its ordinal among the table's rows of its kind."""
+    without one), a counter's or gauge's its ordinal among the table's rows of its kind -- or,
+    for a counter that lives in a CounterEngine, its counter id."""
     line: List[int] = []
     kinds: List[int] = []
     field: List[int] = []
@@ -148,6 +149,7 @@ def influx_table(tree: MetricsTree) -> InfluxTable:
     # a stat row's index is its Stat's series id; a counter's or a gauge's its ordinal among the rows of its kind
     ids = np.asarray(series_index(stats) + [NO_INDEX], np.int64)
     index = scalar_ordinals(ids[np.asarray(stat_ord, np.int64)] if kinds else np.zeros(0, np.int64), kinds_a)
+    index = counter_ids(index, kinds_a, metrics)
     return InfluxTable(np.asarray(line, np.uint32), kinds_a, np.asarray(field, np.uint8), index.astype(np.uint32),
                        *pack_texts(keys), *pack_texts(heads), *pack_texts(tails), metrics, stats,
                        np.asarray(stat_ord, np.uint32))
@@ -162,7 +164,7 @@ def scrape_inputs(table: InfluxTable, summaries=None):
     counters, gauges = scalar_values(table)
     stat_of = np.where(table.kinds == N.KIND_STAT, table.stat_ord.astype(np.int64), -1)
     table, summaries = scrape_rows(table, table.stats, summaries, stat_of)
-    return table, summaries, counters if counters.size else None, gauges if gauges.size else None
+    return table, summaries, nonempty(counters), nonempty(gauges)
 
 
 def _host_bytes(host) -> bytes:

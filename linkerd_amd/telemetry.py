@@ -89,6 +89,8 @@ class StatEngine:
         self.quantile_values: Optional[np.ndarray] = None
         # the sliding window over ended intervals (enable_window): a window.Window of the engine
         self.window = None
+        # the counters.CounterEngine opened over this StatEngine (it sets this): grow takes it along
+        self.counters = None
 
     # registry (MetricsTree.mkStat assigns the id; MetricsTree.prune releases it)
     def register(self) -> int:
@@ -130,7 +132,8 @@ class StatEngine:
         held by Stats stay valid, and register() succeeds again.  The lifetime ``le``
         counters and the last interval's quantile values are kept and extended with zero
         rows; a sliding window moves to the new engine as it is (Window.move_to: no copy), its
-        new ids reading as empty.  Adds from other threads wait for the swap; snapshot calls must not run beside
+        new ids reading as empty, and so does a CounterEngine opened over this StatEngine
+        (CounterEngine.move_to: its values and ids stay).  Adds from other threads wait for the swap; snapshot calls must not run beside
         it.  Tunables set on the old engine (HistogramEngine.set_param) are not carried over."""
         capacity = int(capacity)
         self.flush()
@@ -146,6 +149,8 @@ class StatEngine:
                 new.import_sparse(row_off, entries, totals, first=0)
                 if self.window is not None:
                     self.window.move_to(new)
+                if self.counters is not None:
+                    self.counters.move_to(new)
             except Exception:
                 new.close()
                 raise
@@ -447,18 +452,47 @@ class Metric:
     NONE = _None()
 
     class Counter:
-        """Metric.Counter (Metric.scala:14-20): AtomicLong."""
+        """Metric.Counter (Metric.scala:14-20): AtomicLong.  With ``counters`` (a
+        counters.CounterEngine) the value lives on the GPU under ``counter_id``: incr stages
+        the add (its delta an Int, as the reference's parameter), get is exact and current."""
 
-        def __init__(self):
+        def __init__(self, counters=None):
+            # with a CounterEngine, the monitor of Stat._lock: incr reads the id and stages its
+            # add under it, and _release takes the id away under it
             self._lock = threading.Lock()
-            self._value = 0
+            self._value = 0  # (device-backed: the last value, once the id has been handed back)
+            self._counters = counters
+            self.counter_id = counters.register() if counters is not None else None
 
         def incr(self, delta: int = 1) -> None:
             with self._lock:
-                self._value += int(delta)
+                if self._counters is None:
+                    self._value += int(delta)
+                elif self.counter_id is not None:  # (pruned: like adding to a counter no exporter reads any more)
+                    self._counters.incr(self.counter_id, delta)
 
         def get(self) -> int:
-            return self._value
+            ce, cid = self._counters, self.counter_id  # read once
+            if ce is None or cid is None:
+                return self._value
+            v = ce.bulk_value(cid)  # (a host writer's scrape: one bulk read, not one per counter)
+            return ce.get(cid) if v is None else v
+
+        def _release(self) -> None:
+            """MetricsTree.prune: hand the counter id back.  The id is taken under the
+            counter's lock, so every incr that saw it has already staged its add;
+            CounterEngine.release then flushes those and writes 0 before the id is handed out
+            again.  The counter keeps its last value."""
+            ce = self._counters
+            if ce is None:
+                return
+            with self._lock:
+                cid = self.counter_id
+                if cid is None:
+                    return
+                self._value = ce.get(cid)
+                self.counter_id = None
+            ce.release(cid)
 
     class Stat:
         """Metric.Stat (Metric.scala:22-70) over the GPU engine."""
@@ -546,8 +580,9 @@ class Metric:
 class MetricsTree:
     """MetricsTree.Impl (MetricsTree.scala:38-120)."""
 
-    def __init__(self, engine: Optional[StatEngine] = None):
+    def __init__(self, engine: Optional[StatEngine] = None, counters=None):
         self._engine = engine
+        self._counters = counters  # a counters.CounterEngine: mk_counter makes device-backed counters
         self._trees: Dict[str, "MetricsTree"] = {}  # insertion order
         self._order: Optional[List[str]] = None
         self._tlock = threading.Lock()
@@ -567,7 +602,7 @@ class MetricsTree:
         with self._tlock:
             t = self._trees.get(k)
             if t is None:
-                t = MetricsTree(self._engine)
+                t = MetricsTree(self._engine, self._counters)
                 self._trees[k] = t
             return t
 
@@ -596,7 +631,7 @@ class MetricsTree:
             if isinstance(m, Metric.Counter):
                 return m
             if m is Metric.NONE:
-                self._metric = Metric.Counter()
+                self._metric = Metric.Counter(self._counters)
                 return self._metric
             raise ValueError("non-counter metric already exists")
 
@@ -635,7 +670,7 @@ class MetricsTree:
             k.prune()
         with self._mlock:
             m, self._metric = self._metric, Metric.NONE
-        if isinstance(m, Metric.Stat):
+        if isinstance(m, (Metric.Stat, Metric.Counter)):
             m._release()
 
     def walk(self, prefix: Tuple[str, ...] = ()):
